@@ -18,9 +18,18 @@ and the fused AdamW update with global-norm clipping.  Data is synthetic
 ``--gpus N`` without ``WORLD_SIZE`` in the environment starts the N ranks itself
 (``orion_amd/parallel/launch.py``: one process per GPU, spawned before anything
 touches HIP), so ``python bench.py --gpus 8`` and the driver's
-``torch.distributed.run ... bench.py --gpus 8`` run the same RCCL job.  For N>1 the
-JSON also carries the RCCL all-reduce bus bandwidth of one gradient-arena-sized
-buffer, measured after the timed region.
+``torch.distributed.run ... bench.py --gpus 8`` run the same RCCL job.
+
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--full``
+adds what takes runs of its own after the timed region at N>1: the gradient-bucket
+timeline of one extra step, the RCCL all-reduce bus bandwidth of one gradient-arena-sized
+buffer, and a summary of RCCL's topology log.  ``--dump-outputs DIR`` writes what the last
+timed step returned and updated (loss, gradient norm, seeded samples of the weights, the
+fp32 master and the gradients) as ``DIR/<name>.npy`` for comparing two builds; such a run
+uses the fixed-order kernels of ``ORION_DETERMINISTIC=1`` (``deterministic`` in the result
+line), so its outputs are bit-identical from run to run and it is about 2 % slower than a
+plain run; with ``ORION_DETERMINISTIC=0`` set it keeps the default kernels, whose summation
+order, amplified by AdamW, makes two runs differ (loss by 1e-5 to 3e-4 after 25 steps).
 
 ``--impl torch`` runs the same model on stock PyTorch ops (SDPA, F.layer_norm,
 fp32 master params under bf16 autocast, fused torch AdamW) -- the nanoGPT
@@ -66,7 +75,14 @@ def parse():
                     help="nccl (= RCCL over xGMI, the real run) or gloo (rehearsing N>1 on one GPU)")
     ap.add_argument("--device", choices=["cuda", "cpu"], default="cuda",
                     help="cpu: plumbing rehearsal (reference ops, gloo) -- not a measurement")
-    ap.add_argument("--no-busbw", action="store_true", help="skip the post-run all-reduce probe")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements that take runs of their own after the timed region "
+                         "(N > 1: bucket timeline of one extra step, all-reduce bus bandwidth, RCCL "
+                         "topology summary); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy "
+                         "(float32; large arrays as a fixed seeded sample); runs in deterministic mode")
+    ap.add_argument("--no-busbw", action="store_true", help="with --full: skip the all-reduce probe")
     ap.add_argument("--grad-dtype", choices=["fp32", "bf16"], default="fp32",
                     help="gradient arena dtype (fp32: accumulation and all-reduce in fp32)")
     ap.add_argument("--hip-graph", action="store_true",
@@ -106,6 +122,46 @@ def _replica_checksums(trainer, dev):
     return torch.tensor(out, device=dev, dtype=torch.float64)
 
 
+DUMP_SAMPLE = 1 << 21  # elements kept of each large array: 8 MB as float32
+
+
+def _sample(t, seed):
+    """float32 numpy copy of the flat tensor ``t``, or of DUMP_SAMPLE of its elements at positions
+    drawn once from a seeded CPU generator (the same positions for every run of a given size)."""
+    t = t.detach().reshape(-1)
+    if t.numel() > DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(seed)
+        idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+        t = t[idx.to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def _dump_outputs(out_dir, loss, trainer, model, rank):
+    """What a caller of the timed step holds after the last one: the loss it returned and the
+    state it updated.  Every rank takes part (the ZeRO-1 master is gathered); rank 0 writes.
+    A dump run is a deterministic-mode run (main): bit-identical from run to run."""
+    import numpy as np
+    arrays = {"loss": loss.detach().float().reshape(1).cpu().numpy()}
+    if trainer is not None:
+        trainer.sync_params()
+        arrays["grad_norm"] = np.asarray([trainer.opt.grad_norm()], dtype=np.float32)
+        arrays["params_sample"] = _sample(trainer.arena.params, 1)
+        arrays["master_sample"] = _sample(trainer.full_master(), 2)
+        arrays["grads_sample"] = _sample(trainer.arena.grads, 3)
+    else:
+        flat = torch.cat([p.detach().reshape(-1) for p in model.parameters()])
+        arrays["params_sample"] = _sample(flat, 1)
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def _deterministic() -> bool:
+    from orion_amd.ops.determinism import deterministic
+    return deterministic()
+
+
 def _per_item_walk() -> bool:
     from orion_amd.ops.gemm import per_item_walk
     return per_item_walk()
@@ -113,6 +169,17 @@ def _per_item_walk() -> bool:
 
 def main():
     args = parse()
+    if args.dump_outputs:
+        # Outputs that two runs, or two builds, can be compared by must not depend on the order
+        # in which partial sums meet: the default kernels leave that order open (hipBLASLt
+        # stream-K, fp32 atomics in the embedding backward) and AdamW amplifies the rounding
+        # noise (loss 8.77 vs 8.02 after 110 steps of two default runs).  A dump run therefore
+        # selects the fixed-order kernels (ops/determinism.py) for all its steps; the ranks a
+        # multi-GPU run spawns inherit the setting.  Such a run is about 2 % slower than a plain one
+        # (55.1 vs 54.1 ms per GPT-2 step); the headline figure is that of a plain run.
+        # ORION_DETERMINISTIC=0 in the environment keeps the default kernels for a dump whose
+        # run-to-run noise is accepted.
+        os.environ.setdefault("ORION_DETERMINISTIC", "1")
     from orion_amd.parallel import launch
     if args.gpus > 1 and not launch.in_launched_job():
         # spawn the ranks before this process touches the GPU; exit with the job's status
@@ -136,10 +203,10 @@ def main():
         launch.init_process_group(args.dist_backend if dev.type == "cuda" else "gloo",
                                   dev if dev.type == "cuda" and args.dist_backend == "nccl" else None)
     if world > 1:
-        if args.dist_backend == "nccl":
+        if args.full and args.dist_backend == "nccl":
             # RCCL's topology / channel INFO log of this rank goes to a file, summarised below
             rccl_log = launch.rccl_debug_env(
-                os.environ.get("ORION_BENCH_LOGDIR", os.path.join(ROOT, "gpurun_out", "bench_logs")),
+                os.environ.get("ORION_BENCH_LOGDIR", os.path.join(ROOT, "build", "bench_logs")),
                 rank)
         launch.init_process_group(args.dist_backend, dev if args.dist_backend == "nccl" else None)
     n_tuned = 0
@@ -239,7 +306,9 @@ def main():
         elapsed = float(t)
     final_loss = float(loss)
     busbw = ddp = rccl = replicas = None
-    if world > 1 and args.impl == "native" and trainer.reducer is not None:
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, loss, trainer if args.impl == "native" else None, model, rank)
+    if args.full and world > 1 and args.impl == "native" and trainer.reducer is not None:
         # the bucket timeline comes from ONE extra step after the timed region: the timed steps
         # run without the per-bucket events and the side-stream waits they need
         trainer.reducer.timing = True
@@ -254,7 +323,7 @@ def main():
             allc = [mine]
         replicas = {"identical": all(torch.equal(c, allc[0]) for c in allc),
                     "checksums": [round(float(x), 6) for x in allc[0].tolist()]}
-    if world > 1 and args.impl == "native":
+    if args.full and world > 1 and args.impl == "native":
         # bucket timeline of the extra step: launch -> complete per bucket, exposed tail
         ddp = trainer.reducer.timing_report()
         if ddp is not None:
@@ -296,6 +365,7 @@ def main():
             "dtype": "bf16",
             "data": "synthetic (random token ids), random-init weights",
             "impl": args.impl,
+            "deterministic": _deterministic(),
             "tuned_gemm_entries": n_tuned,
             "hip_graph": bool(args.impl == "native" and trainer.graph_enabled),
             "grad_dtype": str(trainer.arena.grads.dtype).replace("torch.", "") if args.impl == "native" else None,

@@ -84,7 +84,7 @@ class LocalDB(AbstractDB):
         self._tables = set()
         try:
             conn = self._connect()
-            conn.execute("PRAGMA journal_mode=WAL")
+            self._set_wal(conn)
             conn.execute("CREATE TABLE IF NOT EXISTS _orion_indexes "
                          "(coll TEXT, fields TEXT, uniq INTEGER, PRIMARY KEY (coll, fields))")
             conn.execute("CREATE TABLE IF NOT EXISTS _orion_unique "
@@ -93,6 +93,25 @@ class LocalDB(AbstractDB):
         except sqlite3.Error as exc:
             raise DatabaseError(f"cannot open local database {self.path}: {exc}") from exc
         self._open = True
+
+    @staticmethod
+    def _retry_locked(conn, sql):
+        """Execute ``sql``, retrying while SQLite answers "locked" / "busy" at once instead of
+        waiting out the busy timeout (it does so where waiting could deadlock)."""
+        for attempt in range(200):
+            try:
+                conn.execute(sql)
+                return
+            except sqlite3.OperationalError as exc:
+                if "locked" not in str(exc) and "busy" not in str(exc):
+                    raise DatabaseError(str(exc)) from exc
+                time.sleep(0.01 * (1 + attempt % 10))
+        raise DatabaseError("database is locked")
+
+    def _set_wal(self, conn):
+        # Switching a fresh file to WAL needs the database to itself: a second worker doing the
+        # same at that moment is told "locked" at once, so workers that start together retry
+        self._retry_locked(conn, "PRAGMA journal_mode=WAL")
 
     def _connect(self):
         conn = getattr(self._local, "conn", None)
@@ -131,15 +150,7 @@ class LocalDB(AbstractDB):
         return '"' + coll.replace('"', '') + '"'
 
     def _begin(self, conn):
-        for attempt in range(200):
-            try:
-                conn.execute("BEGIN IMMEDIATE")
-                return
-            except sqlite3.OperationalError as exc:
-                if "locked" not in str(exc) and "busy" not in str(exc):
-                    raise DatabaseError(str(exc)) from exc
-                time.sleep(0.01 * (1 + attempt % 10))
-        raise DatabaseError("database is locked")
+        self._retry_locked(conn, "BEGIN IMMEDIATE")
 
     def _uniques(self, conn, coll):
         rows = conn.execute("SELECT fields FROM _orion_indexes WHERE coll=? AND uniq=1", (coll,)).fetchall()

@@ -28,7 +28,11 @@ def _env(tmp_path, **kw):
     env.update(METAOPT_DB_ADDRESS=str(tmp_path / "orion.sqlite"), METAOPT_DB_TYPE="sqlite",
                XDG_CONFIG_HOME=str(tmp_path), TMPDIR=str(tmp_path),  # private lease locks
                SLOT_LOG=str(tmp_path / "slots.jsonl"))
-    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+    # the node is simulated (ORION_GPUS names its slots, the trials run on the CPU): a device list
+    # inherited from the real machine must not meet the leased HIP_VISIBLE_DEVICES in a trial,
+    # where torch refuses a HIP list longer than the ROCR one
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT",
+              "ROCR_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):
         env.pop(k, None)
     env.update(kw)
     return env

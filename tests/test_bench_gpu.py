@@ -49,6 +49,28 @@ def test_bench_single_gpu_contract():
     _check(_json_line(out.stdout), 1, 2, 1, 4)
 
 
+def test_bench_dump_outputs_identical_between_runs(tmp_path):
+    """``--dump-outputs`` selects the fixed-order kernels, so two runs of one build write the same
+    arrays bit for bit (loss, gradient norm, samples of weights / fp32 master / gradients)."""
+    import numpy as np
+    dumps = []
+    for d in ("a", "b"):
+        out = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--micro-batch", "4",
+                              "--dump-outputs", str(tmp_path / d)],
+                             cwd=ROOT, env={k: v for k, v in os.environ.items() if k != "ORION_DETERMINISTIC"},
+                             capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-3000:]
+        rec = _json_line(out.stdout)
+        _check(rec, 1, 3, 1, 4)
+        assert rec["deterministic"] is True
+        dumps.append({f: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    a, b = dumps
+    assert set(a) == {n + ".npy" for n in ("loss", "grad_norm", "params_sample", "master_sample", "grads_sample")}
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert abs(float(a["loss.npy"][0]) - rec["loss"]) <= 5.1e-5
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+
+
 def test_bench_two_ranks_gloo_rehearsal():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "2",

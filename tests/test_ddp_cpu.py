@@ -165,7 +165,7 @@ def test_bench_spawns_its_own_ranks_on_cpu(zero1):
            ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--model", "gpt2-tiny",
                           "--device", "cpu", "--dist-backend", "gloo", "--seq-len", "64",
-                          "--micro-batch", "2", "--steps", "2", "--warmup", "1"]
+                          "--micro-batch", "2", "--steps", "2", "--warmup", "1", "--full"]
                          + (["--zero1"] if zero1 else []),
                          cwd=root, env=env, capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -182,6 +182,27 @@ def test_bench_spawns_its_own_ranks_on_cpu(zero1):
     assert ddp is not None and ddp["exposed_tail_ms"] >= 0
     assert all(done >= ready for _, _, ready, done in ddp["buckets"])
     assert rec["zero1"] == zero1
+
+
+def test_bench_plain_two_rank_run_measures_only_its_steps():
+    """Without ``--full`` an N = 2 run takes no extra step for the bucket timeline and runs no
+    all-reduce probe: those fields of the result line stay empty."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in
+           ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    out = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--model", "gpt2-tiny",
+                          "--device", "cpu", "--dist-backend", "gloo", "--seq-len", "64",
+                          "--micro-batch", "2", "--steps", "2", "--warmup", "1"],
+                         cwd=root, env=env, capture_output=True, text=True, timeout=240)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    rec = json.loads(lines[0])
+    assert rec["n_gpus"] == 2 and rec["steps"] == 2 and rec["ms_per_step"] > 0
+    assert rec["ddp_buckets"] is None and rec["allreduce_busbw_gbps"] is None and rec["rccl"] is None
 
 
 @pytest.mark.parametrize("model", ["gpt2-tiny", "llama-tiny"])
@@ -201,7 +222,7 @@ def test_bench_eight_ranks_on_cpu(model, zero1):
     out = subprocess.run([sys.executable, "bench.py", "--gpus", "8", "--model", model,
                           "--device", "cpu", "--dist-backend", "gloo", "--seq-len", "64",
                           "--micro-batch", "2", "--steps", "2", "--warmup", "1", "--bucket-mb", "0.25",
-                          "--zero1", zero1, "--check-replicas", "--no-busbw"],
+                          "--zero1", zero1, "--check-replicas", "--full", "--no-busbw"],
                          cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

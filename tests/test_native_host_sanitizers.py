@@ -31,7 +31,8 @@ def test_launcher_host_logic_under_asan_ubsan(tmp_path):
 
     with cf.ThreadPoolExecutor(min(6, os.cpu_count() or 2)) as ex:
         objs = list(ex.map(compile_one, SOURCES))
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", *objs, "-fsanitize=address,undefined", "-o", exe],
+    # the sanitizer runtimes are linked for the host only, as the objects were compiled
+    r = subprocess.run([HIPCC, "--offload-arch=gfx950", *objs, *san, "-o", exe],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1",
