@@ -14,6 +14,7 @@
 #include <cstring>
 #include <tuple>
 
+#include "attn_decode_params.h"
 #include "attn_params.h"
 
 // launchers (csrc/*.hip)
@@ -72,6 +73,9 @@ int orion_lmhead_fold(const float*, int, const float*, const int64_t*, long, flo
 int orion_lmhead_bwd_prep(const void*, long, int, long, const int64_t*, long, int, const float*, const float*,
                           const float*, float*, void*, int, hipStream_t);
 int orion_gemm_set_diag(int flags);
+int orion_attn_decode_plan(int, int, int, int, int, int*);
+int orion_attn_decode(const orion::DecodeParams&, int, hipStream_t);
+int orion_kv_append(const orion::AppendParams&, hipStream_t);
 
 namespace {
 
@@ -1091,6 +1095,123 @@ void attn_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor
   unrope();
 }
 
+// ------------------------------------------------------------------ generation (csrc/attn_decode.hip)
+void check_rows16(const Tensor& t, const char* name) {
+  for (int64_t i = 0; i + 1 < t.dim(); ++i)
+    TORCH_CHECK(t.stride(i) % 8 == 0, name, " needs 16-byte aligned rows");
+  TORCH_CHECK(t.stride(-1) == 1 && (uintptr_t)t.data_ptr() % 16 == 0, name,
+              " needs unit stride on the head dim and a 16-byte aligned base");
+}
+
+void check_cache_inputs(const Tensor& k_cache, const Tensor& v_cache, const Tensor& kv_lens) {
+  check_bf16(k_cache, "k_cache"); check_bf16(v_cache, "v_cache");
+  TORCH_CHECK(k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes(), "k_cache / v_cache must be (B, Tmax, Hkv, D)");
+  const int64_t D = k_cache.size(3);
+  TORCH_CHECK(D == 64 || D == 128, "head dim must be 64 or 128, got ", D);
+  TORCH_CHECK(k_cache.size(0) > 0 && k_cache.size(2) > 0 && k_cache.size(1) < (1 << 30), "empty or oversized cache");
+  check_rows16(k_cache, "k_cache"); check_rows16(v_cache, "v_cache");
+  TORCH_CHECK(kv_lens.is_cuda() && kv_lens.scalar_type() == at::kInt && kv_lens.dim() == 1 &&
+                  kv_lens.is_contiguous() && kv_lens.size(0) == k_cache.size(0),
+              "kv_lens must be a contiguous int32 (B,) tensor on the device");
+  TORCH_CHECK(k_cache.device() == v_cache.device() && k_cache.device() == kv_lens.device(), "device mismatch");
+}
+
+// q (B, Hq, D), caches (B, Tmax, Hkv, D), kv_lens (B,) int32 on the device -> o (B, Hq, D).
+// splits = 0: chosen from Tmax, the caller's host-side bound on the length (pass a cache view).
+Tensor attn_decode(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& kv_lens,
+                   double scale, int64_t splits) {
+  check_cache_inputs(k_cache, v_cache, kv_lens);
+  check_bf16(q, "q");
+  TORCH_CHECK(q.dim() == 3 && q.size(0) == k_cache.size(0) && q.size(2) == k_cache.size(3),
+              "q must be (B, Hq, D) matching the cache");
+  TORCH_CHECK(q.size(1) > 0 && q.size(1) % k_cache.size(2) == 0, "Hq must be a multiple of Hkv");
+  TORCH_CHECK(q.device() == k_cache.device(), "device mismatch");
+  TORCH_CHECK(splits >= 0 && splits <= 1024, "splits must be in [0, 1024]");
+  check_rows16(q, "q");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(q.device());
+  const int D = q.size(2);
+  orion::DecodeParams p{};
+  p.B = q.size(0); p.Hq = q.size(1); p.Hkv = k_cache.size(2); p.Tmax = k_cache.size(1);
+  p.splits = orion_attn_decode_plan(p.B, p.Hkv, p.Tmax, D, (int)splits, &p.chunk);
+  auto o = at::empty({p.B, p.Hq, D}, q.options());
+  Tensor ws_o, ws_ml;
+  if (p.splits > 1) {
+    ws_o = at::empty({p.B, p.Hq, p.splits, D}, q.options().dtype(at::kFloat));
+    ws_ml = at::empty({p.B, p.Hq, p.splits, 2}, q.options().dtype(at::kFloat));
+    p.ws_o = ws_o.data_ptr<float>();
+    p.ws_ml = ws_ml.data_ptr<float>();
+  }
+  p.q = (const unsigned short*)q.data_ptr();
+  p.k = (const unsigned short*)k_cache.data_ptr();
+  p.v = (const unsigned short*)v_cache.data_ptr();
+  p.o = (unsigned short*)o.data_ptr();
+  p.kv_lens = kv_lens.data_ptr<int>();
+  p.q_sb = q.stride(0); p.q_sh = q.stride(1);
+  p.k_sb = k_cache.stride(0); p.k_st = k_cache.stride(1); p.k_sh = k_cache.stride(2);
+  p.v_sb = v_cache.stride(0); p.v_st = v_cache.stride(1); p.v_sh = v_cache.stride(2);
+  p.scale_log2 = (float)(scale * 1.4426950408889634);
+  check_launch(orion_attn_decode(p, D, cur_stream()), "attn_decode");
+  return o;
+}
+
+// k_new / v_new (B, T, Hkv, D) -> cache rows kv_lens[b] + t (positions >= Tmax are skipped); with
+// tables k is rotated on the way, and q (B, T, Hq, D) comes back rotated and contiguous (an
+// empty tensor without q).  kv_lens is not changed.
+Tensor kv_append(const Tensor& k_new, const Tensor& v_new, Tensor k_cache, Tensor v_cache, const Tensor& kv_lens,
+                 const c10::optional<Tensor>& q, const c10::optional<Tensor>& cosv,
+                 const c10::optional<Tensor>& sinv) {
+  check_cache_inputs(k_cache, v_cache, kv_lens);
+  check_bf16(k_new, "k_new"); check_bf16(v_new, "v_new");
+  TORCH_CHECK(k_new.dim() == 4 && k_new.sizes() == v_new.sizes() && k_new.size(0) == k_cache.size(0) &&
+                  k_new.size(2) == k_cache.size(2) && k_new.size(3) == k_cache.size(3),
+              "k_new / v_new must be (B, T, Hkv, D) matching the cache");
+  TORCH_CHECK(k_new.device() == k_cache.device() && v_new.device() == k_cache.device(), "device mismatch");
+  check_rows16(k_new, "k_new"); check_rows16(v_new, "v_new");
+  const bool has_q = q.has_value() && q->defined();
+  const bool has_rope = cosv.has_value() && cosv->defined();
+  TORCH_CHECK(has_rope == (sinv.has_value() && sinv->defined()), "kv_append: cos and sin come together");
+  TORCH_CHECK(!has_q || has_rope, "kv_append: q is only taken for rotation (pass cos / sin)");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(k_new.device());
+  orion::AppendParams p{};
+  p.B = k_new.size(0); p.T = k_new.size(1); p.Hkv = k_new.size(2); p.D = k_new.size(3);
+  p.Tmax = k_cache.size(1);
+  TORCH_CHECK((int64_t)p.B * p.T < (1LL << 31) - p.Tmax, "kv_append: too many tokens");
+  if (has_rope) {
+    for (const Tensor* t : {&*cosv, &*sinv})
+      TORCH_CHECK(t->is_cuda() && t->device() == k_new.device() && t->scalar_type() == at::kFloat &&
+                      t->is_contiguous() && t->dim() == 2 && t->size(1) == p.D / 2 && t->size(0) >= p.Tmax &&
+                      (uintptr_t)t->data_ptr() % 16 == 0,
+                  "rope tables must be contiguous fp32 [>= Tmax][D / 2]");
+    p.cosv = cosv->data_ptr<float>();
+    p.sinv = sinv->data_ptr<float>();
+    p.npos = cosv->size(0);
+  }
+  Tensor q_out = at::empty({0}, k_new.options());
+  if (has_q) {
+    check_bf16(*q, "q");
+    TORCH_CHECK(q->dim() == 4 && q->size(0) == p.B && q->size(1) == p.T && q->size(3) == p.D && q->size(2) > 0 &&
+                    q->device() == k_new.device(),
+                "q must be (B, T, Hq, D) matching k_new");
+    check_rows16(*q, "q");
+    p.Hq = q->size(2);
+    q_out = at::empty({p.B, p.T, p.Hq, p.D}, k_new.options());
+    p.q = (const unsigned short*)q->data_ptr();
+    p.q_out = (unsigned short*)q_out.data_ptr();
+    p.q_sb = q->stride(0); p.q_st = q->stride(1); p.q_sh = q->stride(2);
+  }
+  p.k_new = (const unsigned short*)k_new.data_ptr();
+  p.v_new = (const unsigned short*)v_new.data_ptr();
+  p.k_cache = (unsigned short*)k_cache.data_ptr();
+  p.v_cache = (unsigned short*)v_cache.data_ptr();
+  p.kv_lens = kv_lens.data_ptr<int>();
+  p.kn_sb = k_new.stride(0); p.kn_st = k_new.stride(1); p.kn_sh = k_new.stride(2);
+  p.vn_sb = v_new.stride(0); p.vn_st = v_new.stride(1); p.vn_sh = v_new.stride(2);
+  p.kc_sb = k_cache.stride(0); p.kc_st = k_cache.stride(1); p.kc_sh = k_cache.stride(2);
+  p.vc_sb = v_cache.stride(0); p.vc_st = v_cache.stride(1); p.vc_sh = v_cache.stride(2);
+  check_launch(orion_kv_append(p, cur_stream()), "kv_append");
+  return q_out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(orion_amd, m) {
@@ -1132,6 +1253,8 @@ TORCH_LIBRARY(orion_amd, m) {
   m.def("rope_(Tensor(a!) x, Tensor cos, Tensor sin, int pos0, float sign) -> ()");
   m.def("attn_fwd(Tensor q, Tensor k, Tensor v, bool causal, float scale) -> (Tensor, Tensor)");
   m.def("attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, bool causal, float scale, Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, int flags=0, Tensor(d!)? bias_grad=None, Tensor? rope_cos=None, Tensor? rope_sin=None, int rope_pos0=0) -> ()");
+  m.def("attn_decode(Tensor q, Tensor k_cache, Tensor v_cache, Tensor kv_lens, float scale, int splits=0) -> Tensor");
+  m.def("kv_append(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor kv_lens, Tensor? q=None, Tensor? cos=None, Tensor? sin=None) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(orion_amd, CUDA, m) {
@@ -1169,4 +1292,6 @@ TORCH_LIBRARY_IMPL(orion_amd, CUDA, m) {
   m.impl("rope_", &rope_);
   m.impl("attn_fwd", &attn_fwd);
   m.impl("attn_bwd", &attn_bwd);
+  m.impl("attn_decode", &attn_decode);
+  m.impl("kv_append", &kv_append);
 }

@@ -24,6 +24,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
+from .kv_cache import KVCache
 
 
 @dataclass
@@ -201,8 +202,68 @@ class GPT(nn.Module):
         logits = self.lm_head(x[:, [-1], :])
         return logits, None
 
+    def new_cache(self, batch, max_len=None):
+        """An empty :class:`KVCache` for this model on its device (``max_len`` <= block_size)."""
+        cfg = self.config
+        w = self.lm_head.weight
+        return KVCache(cfg.n_layer, batch, min(max_len or cfg.block_size, cfg.block_size), cfg.n_head,
+                       cfg.head_dim, device=w.device, dtype=w.dtype)
+
     @torch.no_grad()
-    def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None):
+    def forward_cached(self, idx, cache):
+        """Logits (B, vocab) of the last position of ``idx`` (B, T), given the ``cache.pos`` tokens
+        already in ``cache``; appends this call's keys / values.  T > 1 is a (chunked) prefill
+        through the flash forward, T == 1 a decode step through ``ops.attention_decode``.  Plain
+        ops throughout: the training-time fused residual sites have no place at M = B."""
+        B, T = idx.shape
+        cfg, tr = self.config, self.transformer
+        assert cache.pos + T <= cfg.block_size, f"sequence {cache.pos + T} > block_size {cfg.block_size}"
+        pos = cache.begin(T)
+        blocks = tr.h
+        H, D = cfg.n_head, cfg.head_dim
+        x = ops.add_broadcast(F.embedding(idx, tr.wte.weight), tr.wpe.weight[pos:pos + T])
+        h = blocks[0].ln_1(x)
+        for i, block in enumerate(blocks):
+            at, ml = block.attn, block.mlp
+            qkv = ops.linear(h, at.c_attn.weight, at.c_attn.bias).view(B, T, 3, H, D)
+            kc, vc = cache.layer(i)
+            ops.kv_append(qkv[:, :, 1], qkv[:, :, 2], kc, vc, cache.start)
+            end = pos + T  # the host's bound of the length: the key split is planned from it
+            if T == 1:
+                y = ops.attention_decode(qkv[:, 0, 0], kc[:, :end], vc[:, :end], cache.lens)
+            else:
+                y = ops.attention(qkv[:, :, 0], kc[:, :end], vc[:, :end], causal=True)
+            a = ops.linear(y.reshape(B, T, H * D), at.c_proj.weight, at.c_proj.bias)
+            x, h = ops.add_layer_norm(x, a, block.ln_2.weight, block.ln_2.bias)
+            m = ops.mlp(h, ml.c_fc.weight, ml.c_fc.bias, ml.c_proj.weight, ml.c_proj.bias)
+            nxt = blocks[i + 1].ln_1 if i + 1 < len(blocks) else tr.ln_f
+            x, h = ops.add_layer_norm(x, m, nxt.weight, nxt.bias)
+        return ops.linear(h[:, -1, :].contiguous(), self.lm_head.weight)
+
+    @staticmethod
+    def _sample(logits, temperature, top_k):
+        logits = logits.float() / max(temperature, 1e-6)
+        if top_k is not None:
+            v, _ = torch.topk(logits, min(top_k, logits.size(-1)))
+            logits[logits < v[:, [-1]]] = -float("inf")
+        return torch.multinomial(F.softmax(logits, dim=-1), num_samples=1)
+
+    @torch.no_grad()
+    def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, use_cache=False):
+        """nanoGPT's sampling loop.  ``use_cache=True`` keeps every layer's keys / values
+        (:class:`KVCache`): the prompt is prefilled once and each new token costs one single-token
+        forward.  Tokens beyond ``block_size`` take the uncached loop below: cropping the window
+        shifts the learned positions, which invalidates a cache."""
+        if use_cache and max_new_tokens > 0 and idx.size(1) < self.config.block_size:
+            n = min(max_new_tokens, self.config.block_size - idx.size(1) + 1)
+            cache = self.new_cache(idx.size(0), idx.size(1) + n - 1)
+            logits = self.forward_cached(idx, cache)
+            for step in range(n):
+                nxt = self._sample(logits, temperature, top_k)
+                idx = torch.cat((idx, nxt), dim=1)
+                if step + 1 < n:
+                    logits = self.forward_cached(nxt, cache)
+            max_new_tokens -= n
         for _ in range(max_new_tokens):
             idx_cond = idx if idx.size(1) <= self.config.block_size else idx[:, -self.config.block_size:]
             logits, _ = self(idx_cond)

@@ -24,6 +24,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..ops import reference as ref
+from .kv_cache import KVCache
 
 
 @dataclass
@@ -167,8 +168,65 @@ class Llama(nn.Module):
         logits = ops.linear(h[:, [-1], :], self.lm_head.weight)
         return logits, None
 
+    def new_cache(self, batch, max_len=None):
+        """An empty :class:`KVCache` for this model on its device (``max_len`` <= max_seq_len)."""
+        cfg = self.config
+        w = self.lm_head.weight
+        return KVCache(cfg.n_layers, batch, min(max_len or cfg.max_seq_len, cfg.max_seq_len), cfg.n_kv_heads,
+                       cfg.head_dim, device=w.device, dtype=w.dtype)
+
     @torch.no_grad()
-    def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None):
+    def forward_cached(self, idx, cache):
+        """Logits (B, vocab) of the last position of ``idx`` (B, T), given the ``cache.pos`` tokens
+        already in ``cache``; appends this call's rotated keys and values.  T > 1 is a (chunked)
+        prefill through the flash forward, T == 1 a decode step through ``ops.attention_decode``.
+        Plain ops throughout: the training-time fused residual sites have no place at M = B."""
+        B, T = idx.shape
+        cfg = self.config
+        assert cache.pos + T <= cfg.max_seq_len
+        pos = cache.begin(T)
+        end = pos + T  # the host's bound of the length: the key split is planned from it
+        Hq, Hkv, D = cfg.n_heads, cfg.n_kv_heads, cfg.head_dim
+        cos, sin = self.rope_cos, self.rope_sin
+        layers = self.layers
+        x = ops.token_embedding(idx, self.embed_tokens.weight)
+        h = layers[0].input_layernorm(x)
+        for i, layer in enumerate(layers):
+            at, ff, pln = layer.self_attn, layer.mlp, layer.post_attention_layernorm
+            qkv = ops.linear(h, at.qkv_proj.weight).view(B, T, Hq + 2 * Hkv, D)
+            kc, vc = cache.layer(i)
+            q = ops.kv_append(qkv[:, :, Hq:Hq + Hkv], qkv[:, :, Hq + Hkv:], kc, vc, cache.start,
+                              q=qkv[:, :, :Hq], cos=cos, sin=sin)
+            if T == 1:
+                y = ops.attention_decode(q[:, 0], kc[:, :end], vc[:, :end], cache.lens)
+            else:
+                y = ops.attention(q, kc[:, :end], vc[:, :end], causal=True)
+            a = ops.linear(y.reshape(B, T, Hq * D), at.o_proj.weight)
+            x, h = ops.add_rms_norm(x, a, pln.weight, pln.eps)
+            m = ops.swiglu_mlp(h, ff.gate_up_proj.weight, ff.down_proj.weight)
+            nxt = layers[i + 1].input_layernorm if i + 1 < len(layers) else self.norm
+            x, h = ops.add_rms_norm(x, m, nxt.weight, nxt.eps)
+        return ops.linear(h[:, -1, :].contiguous(), self.lm_head.weight)
+
+    @torch.no_grad()
+    def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, use_cache=False):
+        """Sampling loop.  ``use_cache=True`` keeps every layer's keys / values
+        (:class:`KVCache`): the prompt is prefilled once and each new token costs one single-token
+        forward; tokens beyond ``max_seq_len`` take the uncached sliding-window loop below."""
+        if use_cache and max_new_tokens > 0 and idx.size(1) < self.config.max_seq_len:
+            n = min(max_new_tokens, self.config.max_seq_len - idx.size(1) + 1)
+            cache = self.new_cache(idx.size(0), idx.size(1) + n - 1)
+            logits = self.forward_cached(idx, cache)
+            for step in range(n):
+                logits = logits.float() / max(temperature, 1e-6)
+                if top_k is not None:
+                    v, _ = torch.topk(logits, min(top_k, logits.size(-1)))
+                    logits[logits < v[:, [-1]]] = -float("inf")
+                nxt = torch.multinomial(torch.softmax(logits, -1), 1)
+                idx = torch.cat((idx, nxt), dim=1)
+                if step + 1 < n:
+                    logits = self.forward_cached(nxt, cache)
+            max_new_tokens -= n
         for _ in range(max_new_tokens):
             cond = idx[:, -self.config.max_seq_len:]
             logits, _ = self(cond)

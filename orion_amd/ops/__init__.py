@@ -322,6 +322,35 @@ def attention(q, k, v, causal=True):
     return ref.attention(q, k, v, causal)
 
 
+# --------------------------------------------------------------------------- generation
+def attention_decode(q, k_cache, v_cache, kv_lens, scale=None, splits=0):
+    """One query per row against a key/value cache: q (B, Hq, D), caches (B, Tmax, Hkv, D), kv_lens
+    (B,) int32 -> (B, Hq, D).  Row b attends keys [0, min(kv_lens[b], Tmax)); what lies beyond is
+    never used (stale NaN included) and an empty row is zeros.  The GPU kernel reads the lengths
+    on the device and splits the keys over ``splits`` workgroups per KV head (0: chosen from
+    Tmax, so pass the cache cut at the host's bound of the length); inference only."""
+    b = _gpu(q)
+    if b == "hip":
+        from .decode import attention_decode_hip
+        return attention_decode_hip(q, k_cache, v_cache, kv_lens, scale, splits)
+    if b == "torch":
+        from .decode import attention_decode_torch
+        return attention_decode_torch(q, k_cache, v_cache, kv_lens, scale)
+    return ref.attention_decode(q, k_cache, v_cache, kv_lens, scale)
+
+
+def kv_append(k_new, v_new, k_cache, v_cache, kv_lens, q=None, cos=None, sin=None):
+    """Write k_new / v_new (B, T, Hkv, D) into the caches at positions kv_lens[b] + t (skipping
+    positions >= Tmax; kv_lens itself is unchanged).  With fp32 tables (``ref.rope_tables``) k is
+    rotated at its position on the way in, and with q (B, T, Hq, D) the rotated q is returned as a
+    new contiguous tensor (else None).  One launch on the GPU; inference only."""
+    b = _gpu(k_new)
+    if b == "hip":
+        from .decode import kv_append_hip
+        return kv_append_hip(k_new, v_new, k_cache, v_cache, kv_lens, q, cos, sin)
+    return ref.kv_append(k_new, v_new, k_cache, v_cache, kv_lens, q, cos, sin)
+
+
 # --------------------------------------------------------------------------- loss
 def cross_entropy(logits, targets, ignore_index=-1):
     b = _gpu(logits)
@@ -352,7 +381,7 @@ __all__ = [
     "attention_qkv", "linear_attention_qkv", "attention", "rope_attention_packed", "linear_rope_attention",
     "cross_entropy", "swiglu_mlp", "linear_residual_layer_norm", "mlp_residual_layer_norm",
     "linear_residual_rms_norm", "swiglu_residual_rms_norm",
-    "linear_cross_entropy",
+    "linear_cross_entropy", "attention_decode", "kv_append",
 ]
 
 

@@ -98,6 +98,50 @@ def attention(q, k, v, causal=True, scale=None):
     return o.to(q.dtype)
 
 
+def attention_decode(q, k_cache, v_cache, kv_lens, scale=None):
+    """One query per row against a key/value cache: q (B, Hq, D), caches (B, Tmax, Hkv, D),
+    kv_lens (B,) -> (B, Hq, D).  Row b attends keys [0, min(kv_lens[b], Tmax)); positions beyond
+    are never read (they may hold anything), and a row of length 0 is zeros."""
+    B, Hq, D = q.shape
+    Tmax, Hkv = k_cache.shape[1], k_cache.shape[2]
+    rep = Hq // Hkv
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    out = torch.zeros(B, Hq, D, dtype=torch.float32, device=q.device)
+    for b, n in enumerate(kv_lens.tolist()):
+        n = max(0, min(int(n), Tmax))
+        if n == 0:
+            continue
+        kf = k_cache[b, :n].float().repeat_interleave(rep, dim=1).transpose(0, 1)  # (Hq, n, D)
+        vf = v_cache[b, :n].float().repeat_interleave(rep, dim=1).transpose(0, 1)
+        s = torch.einsum("hd,hnd->hn", q[b].float(), kf) * scale
+        out[b] = torch.einsum("hn,hnd->hd", s.softmax(-1), vf)
+    return out.to(q.dtype)
+
+
+def kv_append(k_new, v_new, k_cache, v_cache, kv_lens, q=None, cos=None, sin=None):
+    """Write k_new / v_new (B, T, Hkv, D) into the caches (B, Tmax, Hkv, D) at positions
+    kv_lens[b] + t; positions >= Tmax are skipped.  With tables k is rotated at its position
+    (fp32, rounded once) and, given q (B, T, Hq, D), the rotated q is returned as a new tensor
+    (rows of skipped positions are zero).  kv_lens is not changed."""
+    B, T = k_new.shape[:2]
+    Tmax = k_cache.shape[1]
+    assert q is None or cos is not None, "q is only taken for rotation (pass cos / sin)"
+    q_rot = None if q is None else torch.zeros(q.shape, dtype=q.dtype, device=q.device)
+    for b, p0 in enumerate(kv_lens.tolist()):
+        p0 = int(p0)
+        n = max(0, min(T, Tmax - p0))  # tokens of this row that fit
+        if n == 0 or p0 < 0:
+            continue
+        kb = k_new[b:b + 1, :n]
+        if cos is not None:
+            kb = rope(kb, cos[p0:p0 + n], sin[p0:p0 + n])
+            if q is not None:
+                q_rot[b:b + 1, :n] = rope(q[b:b + 1, :n], cos[p0:p0 + n], sin[p0:p0 + n])
+        k_cache[b, p0:p0 + n] = kb[0].to(k_cache.dtype)
+        v_cache[b, p0:p0 + n] = v_new[b, :n].to(v_cache.dtype)
+    return q_rot
+
+
 def cross_entropy(logits, targets, ignore_index=-1):
     return F.cross_entropy(logits.float(), targets, ignore_index=ignore_index)
 

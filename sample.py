@@ -6,6 +6,8 @@
 ``--start`` may be text (encoded with the GPT-2 BPE when ``tiktoken`` is
 available), ``FILE:<path>``, or a comma-separated list of token ids
 (``--start=ids:50256,464``).  Without a tokenizer the token ids are printed.
+``--kv_cache=True`` generates through the key/value cache (one single-token forward per new
+token, ``generate(use_cache=True)``) instead of re-running the whole prefix.
 """
 from __future__ import annotations
 
@@ -18,7 +20,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 DEFAULTS = dict(out_dir="out", start="\n", num_samples=10, max_new_tokens=500, temperature=0.8,
-                top_k=200, seed=1337, device="cuda", ckpt="ckpt.pt")
+                top_k=200, seed=1337, device="cuda", ckpt="ckpt.pt", kv_cache=False)
 
 
 def main(argv=None):
@@ -60,7 +62,8 @@ def main(argv=None):
     x = torch.tensor(ids, dtype=torch.long, device=dev)[None]
     with torch.no_grad():
         for _ in range(cfg["num_samples"]):
-            y = model.generate(x, cfg["max_new_tokens"], temperature=cfg["temperature"], top_k=cfg["top_k"])
+            y = model.generate(x, cfg["max_new_tokens"], temperature=cfg["temperature"], top_k=cfg["top_k"],
+                               use_cache=bool(cfg["kv_cache"]))
             toks = y[0].tolist()
             print(decode(toks) if decode else toks)
             print("---------------")
