@@ -16,6 +16,7 @@
 
 #include "attn_decode_params.h"
 #include "attn_params.h"
+#include "linear_decode_params.h"
 
 // launchers (csrc/*.hip)
 int orion_layernorm_fwd(const void*, const void*, const void*, void*, float*, float*, int, int,
@@ -76,6 +77,7 @@ int orion_gemm_set_diag(int flags);
 int orion_attn_decode_plan(int, int, int, int, int, int*);
 int orion_attn_decode(const orion::DecodeParams&, int, hipStream_t);
 int orion_kv_append(const orion::AppendParams&, hipStream_t);
+int orion_linear_decode(const orion::LinearDecodeParams&, hipStream_t);
 
 namespace {
 
@@ -1212,6 +1214,80 @@ Tensor kv_append(const Tensor& k_new, const Tensor& v_new, Tensor k_cache, Tenso
   return q_out;
 }
 
+// ------------------------------------------------------------------ decode linear (csrc/linear_decode.hip)
+// y (M, Nout) = epi(pro(x) (M, K) . w (N, K)^T) for M <= 16: norm 0 none / 1 LayerNorm / 2 RMSNorm
+// on the rows of x, act 0 none / 1 GELU-tanh / 2 SwiGLU over a packed [gate; up] weight (N = 2 Nout),
+// then + residual.  Written into `out` when given (a static buffer of a captured step).
+Tensor linear_decode(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& bias, int64_t norm,
+                     const c10::optional<Tensor>& norm_w, const c10::optional<Tensor>& norm_b, double eps,
+                     int64_t act, const c10::optional<Tensor>& residual, c10::optional<Tensor> out) {
+  check_bf16(x, "x"); check_bf16(w, "weight");
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == w.size(1), "linear_decode: x (M, K) and weight (N, K), got ",
+              x.sizes(), " and ", w.sizes());
+  const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
+  TORCH_CHECK(M >= 1 && M <= 16, "linear_decode: 1 <= M <= 16 rows, got ", M);
+  TORCH_CHECK(K >= 8 && K % 8 == 0, "linear_decode: K must be a positive multiple of 8, got ", K);
+  TORCH_CHECK(norm >= 0 && norm <= 2 && act >= 0 && act <= 2, "linear_decode: unknown norm / act selector");
+  TORCH_CHECK(N >= 1 && (act != orion::LD_ACT_SWIGLU || N % 2 == 0), "linear_decode: SwiGLU needs an even number of weight rows");
+  TORCH_CHECK(N < (1LL << 31) && K < (1LL << 31), "linear_decode: weight too large");
+  TORCH_CHECK(w.is_contiguous() && (uintptr_t)w.data_ptr() % 16 == 0, "linear_decode: weight must be contiguous and 16-byte aligned");
+  auto rows_ok = [](const Tensor& t) {
+    return t.stride(1) == 1 && (t.size(0) == 1 || t.stride(0) % 8 == 0) && (uintptr_t)t.data_ptr() % 16 == 0;
+  };
+  TORCH_CHECK(rows_ok(x), "linear_decode: rows of x must be 16-byte aligned with unit stride (misaligned rows)");
+  TORCH_CHECK(w.device() == x.device(), "device mismatch");
+  const int64_t Nout = act == orion::LD_ACT_SWIGLU ? N / 2 : N;
+  auto vec = [&](const c10::optional<Tensor>& t, int64_t n, const char* name) -> const unsigned short* {
+    if (!t.has_value() || !t->defined()) return nullptr;
+    check_bf16(*t, name);
+    TORCH_CHECK(t->dim() == 1 && t->size(0) == n && t->is_contiguous() && t->device() == x.device() &&
+                    (uintptr_t)t->data_ptr() % 16 == 0,
+                "linear_decode: ", name, " must be a contiguous 16-byte aligned vector of ", n);
+    return (const unsigned short*)t->data_ptr();
+  };
+  orion::LinearDecodeParams p{};
+  p.bias = vec(bias, N, "bias");
+  p.norm_w = vec(norm_w, K, "norm_weight");
+  p.norm_b = vec(norm_b, K, "norm_bias");
+  TORCH_CHECK((norm != orion::LD_NORM_NONE) == (p.norm_w != nullptr), "linear_decode: norm_weight comes with a norm");
+  TORCH_CHECK(norm == orion::LD_NORM_LAYER || !p.norm_b, "linear_decode: norm_bias is LayerNorm's");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+  Tensor y;
+  if (out.has_value() && out->defined()) {
+    y = *out;
+    check_bf16(y, "out");
+    TORCH_CHECK(y.dim() == 2 && y.size(0) == M && y.size(1) == Nout && y.stride(1) == 1 && y.device() == x.device(),
+                "linear_decode: out must be (M, Nout) with unit column stride");
+  } else {
+    y = at::empty({M, Nout}, x.options());
+  }
+  auto overlaps = [&](const Tensor& t) {
+    const char* a0 = (const char*)y.data_ptr();
+    const char* a1 = a0 + ((M - 1) * y.stride(0) + Nout) * 2;
+    const char* b0 = (const char*)t.data_ptr();
+    const char* b1 = b0 + ((t.size(0) - 1) * t.stride(0) + t.size(1)) * 2;
+    return a0 < b1 && b0 < a1;
+  };
+  TORCH_CHECK(!overlaps(x), "linear_decode: out aliases x");
+  if (residual.has_value() && residual->defined()) {
+    const Tensor& r = *residual;
+    check_bf16(r, "residual");
+    TORCH_CHECK(r.dim() == 2 && r.size(0) == M && r.size(1) == Nout && r.stride(1) == 1 && r.device() == x.device(),
+                "linear_decode: residual must be (M, Nout) with unit column stride");
+    TORCH_CHECK(!overlaps(r), "linear_decode: residual aliases the output (it must be a distinct tensor)");
+    p.res = (const unsigned short*)r.data_ptr();
+    p.res_rs = r.stride(0);
+  }
+  p.x = (const unsigned short*)x.data_ptr();
+  p.w = (const unsigned short*)w.data_ptr();
+  p.y = (unsigned short*)y.data_ptr();
+  p.x_rs = x.stride(0); p.y_rs = y.stride(0);
+  p.M = (int)M; p.K = (int)K; p.Nout = (int)Nout;
+  p.norm = (int)norm; p.act = (int)act; p.eps = (float)eps;
+  check_launch(orion_linear_decode(p, cur_stream()), "linear_decode");
+  return y;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(orion_amd, m) {
@@ -1255,6 +1331,7 @@ TORCH_LIBRARY(orion_amd, m) {
   m.def("attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, bool causal, float scale, Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, int flags=0, Tensor(d!)? bias_grad=None, Tensor? rope_cos=None, Tensor? rope_sin=None, int rope_pos0=0) -> ()");
   m.def("attn_decode(Tensor q, Tensor k_cache, Tensor v_cache, Tensor kv_lens, float scale, int splits=0) -> Tensor");
   m.def("kv_append(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor kv_lens, Tensor? q=None, Tensor? cos=None, Tensor? sin=None) -> Tensor");
+  m.def("linear_decode(Tensor x, Tensor w, Tensor? bias, int norm, Tensor? norm_w, Tensor? norm_b, float eps, int act, Tensor? residual, Tensor(a!)? out=None) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(orion_amd, CUDA, m) {
@@ -1294,4 +1371,5 @@ TORCH_LIBRARY_IMPL(orion_amd, CUDA, m) {
   m.impl("attn_bwd", &attn_bwd);
   m.impl("attn_decode", &attn_decode);
   m.impl("kv_append", &kv_append);
+  m.impl("linear_decode", &linear_decode);
 }

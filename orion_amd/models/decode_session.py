@@ -1,0 +1,204 @@
+"""The decode step on the fused skinny-linear kernels, optionally replayed from a HIP graph.
+
+``forward_cached`` runs a single-token step as ~9 launches per layer through plain ops, library
+GEMMs among them, and is bound by the host's launch rate.  :class:`DecodeSession` runs the same
+step as 6-7 in-tree launches per layer (``ops.linear_decode`` with the norm in its prologue and
+the bias / activation / residual in its epilogue, ``ops.kv_append``, ``ops.attention_decode``)
+and, with ``graph=True``, captures it once and replays it per token.  Everything the step reads
+that changes from token to token lives in device memory: the token in a static buffer, the
+append position and the attention length in ``cache.start`` / ``cache.lens`` (advanced inside
+the step), so a replay needs no new launch parameter.  Prefill is the model's ``forward_cached``
+on the session's cache and is never captured.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn.functional as F
+
+from .. import ops
+from ..ops.decode import MAX_ROWS as MAX_GRAPH_BATCH  # rows of ops.linear_decode's kernel
+
+
+def _projections(model):
+    """(name, weight) of every projection of the decode step."""
+    if hasattr(model, "transformer"):
+        for i, blk in enumerate(model.transformer.h):
+            yield f"h.{i}.attn.c_attn", blk.attn.c_attn.weight
+            yield f"h.{i}.attn.c_proj", blk.attn.c_proj.weight
+            yield f"h.{i}.mlp.c_fc", blk.mlp.c_fc.weight
+            yield f"h.{i}.mlp.c_proj", blk.mlp.c_proj.weight
+    else:
+        for i, layer in enumerate(model.layers):
+            yield f"layers.{i}.self_attn.qkv_proj", layer.self_attn.qkv_proj.weight
+            yield f"layers.{i}.self_attn.o_proj", layer.self_attn.o_proj.weight
+            yield f"layers.{i}.mlp.gate_up_proj", layer.mlp.gate_up_proj.weight
+            yield f"layers.{i}.mlp.down_proj", layer.mlp.down_proj.weight
+    yield "lm_head", model.lm_head.weight
+
+
+class DecodeSession:
+    """One key/value cache, a static (B, 1) token buffer and a static (B, vocab) logits buffer for
+    a :class:`GPT` or :class:`Llama` model.
+
+    ``prefill(idx)`` feeds a prompt (in one or several chunks); ``step(tokens)`` appends one token
+    per row and returns the logits buffer, which the next step overwrites.  With ``graph=True`` on
+    the GPU the first ``step`` warms up on a side stream and captures the step on a single stream
+    (a linear chain of in-tree kernels: no library GEMM is inside); every later ``step`` copies
+    the tokens in and replays.  ``captures`` is 0 or 1, ``replays`` counts the replays;
+    :meth:`reset` empties the cache and keeps the graph."""
+
+    def __init__(self, model, batch, max_len=None, graph=False):
+        cfg = model.config
+        self.model = model
+        self.is_gpt = hasattr(model, "transformer")
+        limit = cfg.block_size if self.is_gpt else cfg.max_seq_len
+        self.batch = int(batch)
+        self.max_len = min(int(max_len or limit), limit)
+        w = model.lm_head.weight
+        self.on_gpu = w.is_cuda
+        self.graph = bool(graph)
+        if self.graph and self.on_gpu:
+            if self.batch > MAX_GRAPH_BATCH:
+                raise ValueError(f"DecodeSession(graph=True): batch {self.batch} > {MAX_GRAPH_BATCH}, the most "
+                                 "rows the skinny linear kernel takes")
+            probes = {}  # one input of the step's shape per K
+            for name, pw in _projections(model):
+                K = pw.shape[1]
+                if K not in probes:
+                    probes[K] = torch.empty(self.batch, K, device=w.device, dtype=w.dtype)
+                if not ops.linear_decode_eligible(probes[K], pw):
+                    raise ValueError(f"DecodeSession(graph=True): {name} {tuple(pw.shape)} {pw.dtype} is not "
+                                     "eligible for ops.linear_decode (bf16 on the HIP backend, K % 8 == 0, "
+                                     "contiguous weight), and a library GEMM must not be captured")
+        self.cache = model.new_cache(self.batch, self.max_len)
+        self.tokens = torch.zeros(self.batch, 1, dtype=torch.long, device=w.device)
+        self.logits = torch.zeros(self.batch, cfg.vocab_size, dtype=w.dtype, device=w.device)
+        self.captures = 0
+        self.replays = 0
+        self._graph = None
+
+    # ------------------------------------------------------------------ prompt
+    @torch.no_grad()
+    def prefill(self, idx):
+        """The model's ``forward_cached`` on this session's cache: logits (B, vocab) of the last
+        position of ``idx`` (B, T); call it again for a chunked prompt."""
+        return self.model.forward_cached(idx, self.cache)
+
+    def reset(self):
+        """Empty the cache for a new prompt; a captured graph stays valid (same buffers)."""
+        self.cache.reset()
+
+    # ------------------------------------------------------------------ one token
+    def _body(self):
+        """One decode step on device state only: advances start / lens, reads ``self.tokens``,
+        writes ``self.logits``."""
+        cache = self.cache
+        cache.start.copy_(cache.lens)
+        cache.lens.add_(1)
+        if self.is_gpt:
+            self._gpt_body()
+        else:
+            self._llama_body()
+
+    def _gpt_body(self):
+        m, cache, B = self.model, self.cache, self.batch
+        cfg, tr = m.config, m.transformer
+        H, D = cfg.n_head, cfg.head_dim
+        x = F.embedding(self.tokens[:, 0], tr.wte.weight) + F.embedding(cache.start, tr.wpe.weight)
+        for i, blk in enumerate(tr.h):
+            at, ml = blk.attn, blk.mlp
+            qkv = ops.linear_decode(x, at.c_attn.weight, at.c_attn.bias, norm="layer", norm_weight=blk.ln_1.weight,
+                                    norm_bias=blk.ln_1.bias).view(B, 1, 3, H, D)
+            kc, vc = cache.layer(i)
+            ops.kv_append(qkv[:, :, 1], qkv[:, :, 2], kc, vc, cache.start)
+            # the whole cache view: the key split is planned from max_len once and never changes
+            y = ops.attention_decode(qkv[:, 0, 0], kc, vc, cache.lens)
+            x = ops.linear_decode(y.view(B, H * D), at.c_proj.weight, at.c_proj.bias, residual=x)
+            h = ops.linear_decode(x, ml.c_fc.weight, ml.c_fc.bias, norm="layer", norm_weight=blk.ln_2.weight,
+                                  norm_bias=blk.ln_2.bias, act="gelu")
+            x = ops.linear_decode(h, ml.c_proj.weight, ml.c_proj.bias, residual=x)
+        ops.linear_decode(x, m.lm_head.weight, norm="layer", norm_weight=tr.ln_f.weight, norm_bias=tr.ln_f.bias,
+                          out=self.logits)
+
+    def _llama_body(self):
+        m, cache, B = self.model, self.cache, self.batch
+        cfg = m.config
+        Hq, Hkv, D = cfg.n_heads, cfg.n_kv_heads, cfg.head_dim
+        cos, sin = m.rope_cos, m.rope_sin
+        x = F.embedding(self.tokens[:, 0], m.embed_tokens.weight)
+        for i, layer in enumerate(m.layers):
+            at, ff = layer.self_attn, layer.mlp
+            ln1, ln2 = layer.input_layernorm, layer.post_attention_layernorm
+            qkv = ops.linear_decode(x, at.qkv_proj.weight, norm="rms", norm_weight=ln1.weight,
+                                    eps=ln1.eps).view(B, 1, Hq + 2 * Hkv, D)
+            kc, vc = cache.layer(i)
+            q = ops.kv_append(qkv[:, :, Hq:Hq + Hkv], qkv[:, :, Hq + Hkv:], kc, vc, cache.start,
+                              q=qkv[:, :, :Hq], cos=cos, sin=sin)
+            y = ops.attention_decode(q[:, 0], kc, vc, cache.lens)
+            x = ops.linear_decode(y.view(B, Hq * D), at.o_proj.weight, residual=x)
+            h = ops.linear_decode(x, ff.gate_up_proj.weight, norm="rms", norm_weight=ln2.weight, eps=ln2.eps,
+                                  act="swiglu")
+            x = ops.linear_decode(h, ff.down_proj.weight, residual=x)
+        ops.linear_decode(x, m.lm_head.weight, norm="rms", norm_weight=m.norm.weight, eps=m.norm.eps,
+                          out=self.logits)
+
+    @torch.no_grad()
+    def step(self, tokens):
+        """Append ``tokens`` (B,) or (B, 1) and return the static logits buffer (B, vocab) of the
+        next position.  Raises ``ValueError`` before any launch when the cache is full."""
+        cache = self.cache
+        if cache.pos + 1 > cache.max_len:
+            raise ValueError(f"KVCache overflow: {cache.pos} cached + 1 new tokens > max_len {cache.max_len}")
+        self.tokens.copy_(tokens.reshape(self.batch, 1))
+        if not (self.graph and self.on_gpu):
+            self._body()
+        elif self._graph is not None:
+            self._graph.replay()
+            self.replays += 1
+        else:
+            # eager warm-up on a side stream (lazy initialisations must not happen inside a
+            # capture), the lengths put back afterwards; then the capture on one stream.  A capture
+            # launches nothing, so the first replay is this call's step.
+            lens, start = cache.lens.clone(), cache.start.clone()
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                self._body()
+            torch.cuda.current_stream().wait_stream(side)
+            cache.lens.copy_(lens)
+            cache.start.copy_(start)
+            g = torch.cuda.CUDAGraph()
+            torch.cuda.synchronize()
+            with torch.cuda.graph(g):
+                self._body()
+            self._graph = g
+            self.captures = 1
+            g.replay()
+        cache.pos += 1
+        return self.logits
+
+    # ------------------------------------------------------------------ sampling loop
+    @torch.no_grad()
+    def generate(self, idx, n, temperature=1.0, top_k=None):
+        """Prefill ``idx`` (B, T) and sample ``n`` tokens (T + n - 1 <= max_len): (B, T + n).
+        Sampling stays outside the captured step, on the static logits, and the new tokens go
+        into a preallocated output."""
+        B, T = idx.shape
+        out = torch.empty(B, T + n, dtype=idx.dtype, device=idx.device)
+        out[:, :T] = idx
+        logits = self.prefill(idx)
+        for i in range(n):
+            nxt = sample_logits(logits, temperature, top_k)
+            out[:, T + i:T + i + 1] = nxt
+            if i + 1 < n:
+                logits = self.step(nxt)
+        return out
+
+
+def sample_logits(logits, temperature=1.0, top_k=None):
+    """The models' sampling rule on (B, vocab) logits -> (B, 1) token ids."""
+    logits = logits.float() / max(temperature, 1e-6)
+    if top_k is not None:
+        v, _ = torch.topk(logits, min(top_k, logits.size(-1)))
+        logits[logits < v[:, [-1]]] = -float("inf")
+    return torch.multinomial(torch.softmax(logits, dim=-1), num_samples=1)

@@ -175,6 +175,11 @@ class Llama(nn.Module):
         return KVCache(cfg.n_layers, batch, min(max_len or cfg.max_seq_len, cfg.max_seq_len), cfg.n_kv_heads,
                        cfg.head_dim, device=w.device, dtype=w.dtype)
 
+    def decode_session(self, batch, max_len=None, graph=False):
+        """A :class:`DecodeSession` for this model: the fused decode step, captured when ``graph``."""
+        from .decode_session import DecodeSession
+        return DecodeSession(self, batch, max_len, graph=graph)
+
     @torch.no_grad()
     def forward_cached(self, idx, cache):
         """Logits (B, vocab) of the last position of ``idx`` (B, T), given the ``cache.pos`` tokens
@@ -212,8 +217,18 @@ class Llama(nn.Module):
     def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, use_cache=False):
         """Sampling loop.  ``use_cache=True`` keeps every layer's keys / values
         (:class:`KVCache`): the prompt is prefilled once and each new token costs one single-token
-        forward; tokens beyond ``max_seq_len`` take the uncached sliding-window loop below."""
-        if use_cache and max_new_tokens > 0 and idx.size(1) < self.config.max_seq_len:
+        forward; tokens beyond ``max_seq_len`` take the uncached sliding-window loop below.
+        ``use_cache="fused"`` runs the cached tokens through a :class:`DecodeSession` (the fused
+        skinny-linear decode step), ``"graph"`` additionally replays that step from one captured
+        HIP graph."""
+        if isinstance(use_cache, str) and use_cache not in ("fused", "graph"):
+            raise ValueError(f"use_cache must be False, True, 'fused' or 'graph', got {use_cache!r}")
+        if isinstance(use_cache, str) and max_new_tokens > 0 and idx.size(1) < self.config.max_seq_len:
+            n = min(max_new_tokens, self.config.max_seq_len - idx.size(1) + 1)
+            sess = self.decode_session(idx.size(0), idx.size(1) + n - 1, graph=use_cache == "graph")
+            idx = sess.generate(idx, n, temperature, top_k)
+            max_new_tokens -= n
+        elif use_cache and max_new_tokens > 0 and idx.size(1) < self.config.max_seq_len:
             n = min(max_new_tokens, self.config.max_seq_len - idx.size(1) + 1)
             cache = self.new_cache(idx.size(0), idx.size(1) + n - 1)
             logits = self.forward_cached(idx, cache)

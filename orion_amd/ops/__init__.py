@@ -351,6 +351,60 @@ def kv_append(k_new, v_new, k_cache, v_cache, kv_lens, q=None, cos=None, sin=Non
     return ref.kv_append(k_new, v_new, k_cache, v_cache, kv_lens, q, cos, sin)
 
 
+def linear_decode_eligible(x, weight):
+    """Whether the skinny decode kernel (csrc/linear_decode.hip) takes this input on the HIP
+    backend: bf16 GPU tensors, at most 16 rows of x with 16-byte aligned unit-stride rows,
+    K % 8 == 0, a contiguous weight."""
+    if not x.is_cuda or _BACKEND != "hip":
+        return False
+    from .decode import linear_decode_eligible as ok
+    return ok(x, weight)
+
+
+def _linear_decode_composed(x, weight, bias, norm, norm_weight, norm_bias, eps, act, residual):
+    """The same function on the plain ops of this module (each dispatching on its own)."""
+    h = x
+    if norm == "layer":
+        h = layer_norm(x, norm_weight, norm_bias, eps)
+    elif norm == "rms":
+        h = rms_norm(x, norm_weight, eps)
+    if act == "gelu":
+        y = linear(h, weight)
+        y = gelu(y) if bias is None else bias_gelu(y, bias)
+    else:
+        y = linear(h, weight, bias)
+        if act == "swiglu":
+            y = swiglu(y)
+    return y if residual is None else y + residual.to(y.dtype)
+
+
+def linear_decode(x, weight, bias=None, *, norm=None, norm_weight=None, norm_bias=None, eps=1e-5, act=None,
+                  residual=None, out=None):
+    """The decode step's linear layer, act(norm(x) W^T + bias) + residual, for x (..., K) with few
+    rows and weight (N, K): ``norm`` in {None, "layer", "rms"} on the rows of x (``norm_weight``,
+    LayerNorm's optional ``norm_bias``), ``act`` in {None, "gelu", "swiglu"} (SwiGLU over a packed
+    [gate; up] weight of 2F rows -> (..., F)), ``residual`` a distinct tensor of the output's
+    shape.  On the GPU one weight-streaming launch when :func:`linear_decode_eligible` (at most 16
+    rows), else the plain ops composed; ``out`` (rows, Nout) takes the result in place.
+    Inference only."""
+    assert norm in (None, "layer", "rms") and act in (None, "gelu", "swiglu"), (norm, act)
+    assert (norm is None) == (norm_weight is None), "norm_weight comes with a norm"
+    from .decode import _no_grad
+    _no_grad(x, weight, bias, norm_weight, norm_bias, residual)
+    b = _gpu(x)
+    if b == "hip" and linear_decode_eligible(x, weight):
+        from .decode import linear_decode_hip
+        return linear_decode_hip(x, weight, bias, norm, norm_weight, norm_bias, eps, act, residual, out)
+    if b is None:
+        y = ref.linear_decode(x, weight, bias, norm, norm_weight, norm_bias, eps, act, residual)
+    else:
+        y = _linear_decode_composed(x, weight, bias, norm, norm_weight, norm_bias, eps, act, residual)
+    if out is None:
+        return y
+    out.copy_(y.reshape(out.shape))
+    return out.view(y.shape)
+
+
 # --------------------------------------------------------------------------- loss
 def cross_entropy(logits, targets, ignore_index=-1):
     b = _gpu(logits)
@@ -381,7 +435,7 @@ __all__ = [
     "attention_qkv", "linear_attention_qkv", "attention", "rope_attention_packed", "linear_rope_attention",
     "cross_entropy", "swiglu_mlp", "linear_residual_layer_norm", "mlp_residual_layer_norm",
     "linear_residual_rms_norm", "swiglu_residual_rms_norm",
-    "linear_cross_entropy", "attention_decode", "kv_append",
+    "linear_cross_entropy", "attention_decode", "kv_append", "linear_decode", "linear_decode_eligible",
 ]
 
 
@@ -430,6 +484,6 @@ def _guarded(fn):
 for _name in ("layer_norm", "add_layer_norm", "add_rms_norm", "linear", "rms_norm", "bias_gelu",
               "gelu_linear", "mlp", "swiglu_mlp", "embed_layer_norm", "token_embedding", "add_broadcast",
               "linear_attention_qkv", "linear_rope_attention",
-              "linear_cross_entropy"):
+              "linear_cross_entropy", "linear_decode"):
     globals()[_name] = _guarded(globals()[_name])
 del _name

@@ -1,7 +1,9 @@
-"""Generation-time ops over the HIP kernels of csrc/attn_decode.hip: single-query attention
-against a key/value cache (split over keys, lengths read on the device) and the cache append
-with optional RoPE.  Inference only: there is no backward, and an input that requires grad
-while gradients are enabled is an error rather than a silently dropped graph."""
+"""Generation-time ops over the HIP kernels of csrc/attn_decode.hip and csrc/linear_decode.hip:
+single-query attention against a key/value cache (split over keys, lengths read on the device),
+the cache append with optional RoPE, and the skinny (M <= 16) linear layer with a fused norm
+prologue and bias / activation / residual epilogue.  Inference only: there is no backward, and
+an input that requires grad while gradients are enabled is an error rather than a silently
+dropped graph."""
 from __future__ import annotations
 
 import math
@@ -13,8 +15,48 @@ from ._ext import C
 
 def _no_grad(*tensors):
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
-        raise RuntimeError("attention_decode / kv_append are inference-only ops: inputs must not "
-                           "require grad (run under torch.no_grad())")
+        raise RuntimeError("attention_decode / kv_append / linear_decode are inference-only ops: inputs "
+                           "must not require grad (run under torch.no_grad())")
+
+
+NORMS = {None: 0, "layer": 1, "rms": 2}
+ACTS = {None: 0, "gelu": 1, "swiglu": 2}
+MAX_ROWS = 16  # rows of one MFMA tile: the kernel's upper bound on M
+
+
+def _rows16(t):
+    return t.stride(-1) == 1 and (t.shape[0] == 1 or t.stride(0) % 8 == 0) and t.data_ptr() % 16 == 0
+
+
+def linear_decode_eligible(x, weight):
+    """Whether csrc/linear_decode.hip takes x (..., K) (at most 16 rows that flatten to a view with
+    16-byte aligned, unit-stride rows) against weight (N, K): both bf16 on the GPU, K % 8 == 0,
+    weight contiguous."""
+    if not (x.is_cuda and weight.is_cuda and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16):
+        return False
+    if weight.dim() != 2 or x.dim() < 1 or x.shape[-1] != weight.shape[1] or not weight.is_contiguous():
+        return False
+    K = weight.shape[1]
+    if K < 8 or K % 8 or weight.data_ptr() % 16 or x.numel() == 0 or x.numel() // K > MAX_ROWS:
+        return False
+    try:
+        x2 = x.view(-1, K)
+    except RuntimeError:
+        return False
+    return _rows16(x2)
+
+
+def linear_decode_hip(x, weight, bias=None, norm=None, norm_weight=None, norm_bias=None, eps=1e-5, act=None,
+                      residual=None, out=None):
+    """One launch: act(norm(x) W^T + bias) + residual for x (..., K) of at most 16 rows -> (..., Nout);
+    ``out`` (rows, Nout) receives the result in place (a static buffer of a captured step)."""
+    _no_grad(x, weight, bias, norm_weight, norm_bias, residual)
+    K = weight.shape[1]
+    n_out = weight.shape[0] // 2 if act == "swiglu" else weight.shape[0]
+    r2 = None if residual is None else residual.view(-1, n_out)
+    y = C().linear_decode(x.view(-1, K), weight, bias, NORMS[norm], norm_weight, norm_bias, float(eps), ACTS[act],
+                          r2, out)
+    return y.view(*x.shape[:-1], n_out)
 
 
 def attention_decode_hip(q, k_cache, v_cache, kv_lens, scale=None, splits=0):

@@ -142,6 +142,30 @@ def kv_append(k_new, v_new, k_cache, v_cache, kv_lens, q=None, cos=None, sin=Non
     return q_rot
 
 
+def linear_decode(x, weight, bias=None, norm=None, norm_weight=None, norm_bias=None, eps=1e-5, act=None,
+                  residual=None):
+    """The decode step's fused linear as a composition of the functions above:
+    act(norm(x) W^T + bias) + residual with norm in {None, "layer", "rms"} on the rows of x and
+    act in {None, "gelu", "swiglu"} (SwiGLU over a packed [gate; up] weight of 2F rows -> F)."""
+    assert norm in (None, "layer", "rms") and act in (None, "gelu", "swiglu"), (norm, act)
+    h = x
+    if norm == "layer":
+        h = layer_norm(x, norm_weight, norm_bias, eps)
+    elif norm == "rms":
+        h = rms_norm(x, norm_weight, eps)
+    y = F.linear(h, weight.to(h.dtype))
+    if act == "gelu":
+        y = gelu_tanh(y) if bias is None else bias_gelu(y, bias)
+    else:
+        if bias is not None:
+            y = y + bias.to(y.dtype)
+        if act == "swiglu":
+            y = swiglu(*y.chunk(2, dim=-1))
+    if residual is not None:
+        y = y + residual.to(y.dtype)
+    return y
+
+
 def cross_entropy(logits, targets, ignore_index=-1):
     return F.cross_entropy(logits.float(), targets, ignore_index=ignore_index)
 

@@ -7,7 +7,9 @@
 available), ``FILE:<path>``, or a comma-separated list of token ids
 (``--start=ids:50256,464``).  Without a tokenizer the token ids are printed.
 ``--kv_cache=True`` generates through the key/value cache (one single-token forward per new
-token, ``generate(use_cache=True)``) instead of re-running the whole prefix.
+token, ``generate(use_cache=True)``) instead of re-running the whole prefix; ``--kv_cache=fused``
+runs those tokens on the fused decode step and ``--kv_cache=graph`` replays that step from one
+captured HIP graph (``generate(use_cache="fused" / "graph")``).
 """
 from __future__ import annotations
 
@@ -60,10 +62,13 @@ def main(argv=None):
     else:
         ids = [50256 if model.config.vocab_size > 50256 else 0]
     x = torch.tensor(ids, dtype=torch.long, device=dev)[None]
+    kv = cfg["kv_cache"]
+    if isinstance(kv, str) and kv not in ("fused", "graph"):
+        raise ValueError(f"--kv_cache must be True, False, fused or graph, got {kv!r}")
     with torch.no_grad():
         for _ in range(cfg["num_samples"]):
             y = model.generate(x, cfg["max_new_tokens"], temperature=cfg["temperature"], top_k=cfg["top_k"],
-                               use_cache=bool(cfg["kv_cache"]))
+                               use_cache=kv if kv in ("fused", "graph") else bool(kv))
             toks = y[0].tolist()
             print(decode(toks) if decode else toks)
             print("---------------")

@@ -2,13 +2,18 @@
 """Generation benchmark: (i) the split-KV decode attention kernel (csrc/attn_decode.hip) beside
 torch SDPA on the same cache view, at the GPT-2 and the Llama-GQA decode shapes; (ii) generated
 tokens/s of ``gpt2`` with and without the KV cache (prompt 64 + 256 new tokens at B 1 and 8, and
-a long-context point, prompt 768 at B 8), the two arms alternating.
+a long-context point, prompt 768 at B 8) and on the fused decode step, eager (``fused``) and
+replayed from one captured HIP graph (``graph``), the arms alternating; (iii) the skinny decode
+linear (csrc/linear_decode.hip) at every projection shape of ``gpt2`` and of the Llama-2-7B layer
+at M = 1, 8, 16 beside the same call through ``F.linear`` with its separate norm / activation /
+residual launches.
 
 The kernel timing rotates over enough distinct caches to exceed the 256 MB Infinity Cache, so
 every call streams its K and V from HBM; bytes/s counts the K + V actually read (one pass per
-KV head).  Prints one JSON line per measurement.
+KV head); the linear timing rotates over weights the same way and counts the weight bytes.
+Prints one JSON line per measurement.
 
-usage: python scripts/bench_decode.py [--kernel 0|1] [--generate 0|1] [--rounds N]
+usage: python scripts/bench_decode.py [--kernel 0|1] [--linear 0|1] [--generate 0|1] [--rounds N]
 """
 import argparse
 import json
@@ -18,6 +23,7 @@ import sys
 import time
 
 import torch
+import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from orion_amd import ops  # noqa: E402
@@ -81,11 +87,94 @@ def bench_kernel(name, B, Hq, Hkv, D, T, rounds):
     print(json.dumps(res), flush=True)
 
 
+# (name, N, K, norm, act, bias, residual): the decode step's projections with what each fuses
+LINEAR_SHAPES = {
+    "gpt2": [("c_attn", 2304, 768, "layer", None, True, False), ("attn.c_proj", 768, 768, None, None, True, True),
+             ("c_fc", 3072, 768, "layer", "gelu", True, False), ("mlp.c_proj", 768, 3072, None, None, True, True),
+             ("lm_head", 50304, 768, "layer", None, False, False)],
+    "llama2-7b": [("qkv_proj", 12288, 4096, "rms", None, False, False),
+                  ("o_proj", 4096, 4096, None, None, False, True),
+                  ("gate_up_proj", 22016, 4096, "rms", "swiglu", False, False),
+                  ("down_proj", 4096, 11008, None, None, False, True)],
+}
+
+
+def bench_linear(model, name, N, K, norm, act, bias, residual, M, rounds):
+    g = torch.Generator(device="cuda").manual_seed(0)
+
+    def r(*s):
+        return torch.randn(*s, device="cuda", generator=g).to(torch.bfloat16)
+
+    w_bytes = N * K * 2
+    n_buf = max(2, math.ceil(512e6 / w_bytes))
+    ws = [r(N, K) for _ in range(n_buf)]
+    n_out = N // 2 if act == "swiglu" else N
+    x, b, res = r(M, K), (r(N) if bias else None), (r(M, n_out) if residual else None)
+    nw, nb = (r(K) if norm else None), (r(K) if norm == "layer" else None)
+
+    def hip(i):
+        return ops.linear_decode(x, ws[i % n_buf], b, norm=norm, norm_weight=nw, norm_bias=nb, act=act, residual=res)
+
+    def stock(i):
+        h = x
+        if norm == "layer":
+            h = F.layer_norm(x, (K,), nw, nb, 1e-5)
+        elif norm == "rms":
+            xf = x.float()
+            h = (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + 1e-5)).to(x.dtype) * nw
+        y = F.linear(h, ws[i % n_buf], b)
+        if act == "gelu":
+            y = F.gelu(y, approximate="tanh")
+        elif act == "swiglu":
+            gate, up = y.chunk(2, dim=-1)
+            y = F.silu(gate) * up
+        return y if res is None else y + res
+
+    assert ops.linear_decode_eligible(x, ws[0])
+    err = (hip(0).float() - stock(0).float()).abs().max().item()
+    us = _time_us({"hip": hip, "f_linear": stock}, rounds)
+    out = dict(bench="linear_decode", model=model, proj=name, M=M, N=N, K=K, norm=norm, act=act, bias=bias,
+               residual=residual, w_mbytes=round(w_bytes / 1e6, 2), rotating_weights=n_buf,
+               max_abs_diff_vs_f_linear=round(err, 4), hbm_copy_TBs=HBM_COPY_TBS)
+    for k, v in us.items():
+        out[f"{k}_us"] = round(v, 2)
+        out[f"{k}_GBs"] = round(w_bytes / v / 1e3, 1)
+    out["hip_over_copy_rate"] = round(out["hip_GBs"] / 1e3 / HBM_COPY_TBS, 3)
+    out["speedup"] = round(us["f_linear"] / us["hip"], 2)
+    print(json.dumps(out), flush=True)
+
+
+def bench_graph_steady(model, B, prompt_len, new_tokens):
+    """The graph arm without its capture: per-token time of the sampling loop on a captured
+    session, and of the replay alone (the rest is the sampling launches)."""
+    from orion_amd.models.decode_session import sample_logits
+    prompt = torch.randint(0, 50257, (B, prompt_len), device="cuda")
+    sess = model.decode_session(B, prompt_len + new_tokens, graph=True)
+    logits = sess.prefill(prompt)
+    nxt = sample_logits(logits, 1.0, 200)
+    sess.step(nxt)  # warm-up + capture
+    n = new_tokens - 2
+    res = {}
+    for what in ("token", "replay"):
+        sess.reset()
+        logits = sess.prefill(prompt)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            if what == "token":
+                nxt = sample_logits(logits, 1.0, 200)
+            logits = sess.step(nxt)
+        torch.cuda.synchronize()
+        res[what] = (time.perf_counter() - t0) / n
+    assert sess.captures == 1
+    return res
+
+
 def bench_generate(B, prompt_len, new_tokens, rounds):
     torch.manual_seed(0)
     model = build_gpt2("gpt2").to("cuda").to(torch.bfloat16).eval()
     prompt = torch.randint(0, 50257, (B, prompt_len), device="cuda")
-    arms = {"cached": True, "uncached": False}
+    arms = {"cached": True, "uncached": False, "fused": "fused", "graph": "graph"}
     for use_cache in arms.values():  # warm-up: every shape of both arms
         model.generate(prompt, new_tokens, top_k=200, use_cache=use_cache)
     torch.cuda.synchronize()
@@ -104,12 +193,20 @@ def bench_generate(B, prompt_len, new_tokens, rounds):
         res[f"{k}_s"] = round(v, 4)
         res[f"{k}_tok_per_s"] = round(B * new_tokens / v, 1)
     res["cached_over_uncached"] = round(med["uncached"] / med["cached"], 2)
+    best = min(med["cached"], med["uncached"])  # the faster of the two arms that predate the fused step
+    res["fused_over_best_baseline"] = round(best / med["fused"], 2)
+    res["graph_over_best_baseline"] = round(best / med["graph"], 2)
+    steady = bench_graph_steady(model, B, prompt_len, new_tokens)
+    res["graph_steady_ms_per_token"] = round(steady["token"] * 1e3, 3)
+    res["graph_replay_ms_per_token"] = round(steady["replay"] * 1e3, 3)
+    res["graph_sampling_ms_per_token"] = round((steady["token"] - steady["replay"]) * 1e3, 3)
     print(json.dumps(res), flush=True)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--kernel", type=int, default=1)
+    ap.add_argument("--linear", type=int, default=1)
     ap.add_argument("--generate", type=int, default=1)
     ap.add_argument("--rounds", type=int, default=5)
     a = ap.parse_args()
@@ -120,6 +217,11 @@ def main():
         if a.kernel:
             for name, s in SHAPES.items():
                 bench_kernel(name, rounds=max(a.rounds, 5) * 2, **s)
+        if a.linear:
+            for model, shapes in LINEAR_SHAPES.items():
+                for shape in shapes:
+                    for M in (1, 8, 16):
+                        bench_linear(model, *shape, M=M, rounds=max(a.rounds, 5))
         if a.generate:
             for B in (1, 8):
                 bench_generate(B, 64, 256, a.rounds)
