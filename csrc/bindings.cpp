@@ -17,6 +17,7 @@
 #include "attn_decode_params.h"
 #include "attn_params.h"
 #include "linear_decode_params.h"
+#include "sample_params.h"
 
 // launchers (csrc/*.hip)
 int orion_layernorm_fwd(const void*, const void*, const void*, void*, float*, float*, int, int,
@@ -78,6 +79,7 @@ int orion_attn_decode_plan(int, int, int, int, int, int*);
 int orion_attn_decode(const orion::DecodeParams&, int, hipStream_t);
 int orion_kv_append(const orion::AppendParams&, hipStream_t);
 int orion_linear_decode(const orion::LinearDecodeParams&, hipStream_t);
+int orion_sample_tokens(const orion::SampleParams&, hipStream_t);
 
 namespace {
 
@@ -1288,6 +1290,76 @@ Tensor linear_decode(const Tensor& x, const Tensor& w, const c10::optional<Tenso
   return y;
 }
 
+// ------------------------------------------------------------------ sampling (csrc/sample.hip)
+// One token per row of logits (B, V) bf16 by the models' rule: softmax(logits / T) over the entries
+// >= the top_k-th largest, drawn by inverting the CDF in index order at u.  params (2,) int32 on
+// the device holds the fp32 bits of T and top_k; u (B,) fp32 is given, or comes from Philox with
+// the int64 `seed` (1,) as key and (positions[b], b, 0, 0) as counter.  The token goes to `out`
+// (B,) or (B, 1) int64 and, with `history` (B, L), to history[b, positions[b]] (skipped when the
+// position is >= L); `u_out` (B,) fp32 receives the u that was used.
+Tensor sample_tokens(const Tensor& logits, const Tensor& params, const c10::optional<Tensor>& u,
+                     const c10::optional<Tensor>& seed, const c10::optional<Tensor>& positions,
+                     c10::optional<Tensor> out, c10::optional<Tensor> history, c10::optional<Tensor> u_out) {
+  check_bf16(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.size(1) >= 1, "sample_tokens: logits must be (B, V)");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V < (1LL << 31) && B < (1LL << 31), "sample_tokens: logits too large");
+  TORCH_CHECK(logits.stride(1) == 1, "sample_tokens: logits need unit stride on the vocabulary (inner stride)");
+  const auto dev = logits.device();
+  auto given = [](const c10::optional<Tensor>& t) { return t.has_value() && t->defined(); };
+  auto check_vec = [&](const Tensor& t, at::ScalarType ty, int64_t n, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.device() == dev, "sample_tokens: ", name, " must be on the logits' device");
+    TORCH_CHECK(t.scalar_type() == ty, "sample_tokens: ", name, " has the wrong dtype (", t.scalar_type(), ")");
+    TORCH_CHECK(t.dim() == 1 && t.size(0) == n && t.is_contiguous(), "sample_tokens: ", name,
+                " must be a contiguous vector of ", n);
+  };
+  check_vec(params, at::kInt, 2, "params");
+  orion::SampleParams p{};
+  if (given(u)) {
+    check_vec(*u, at::kFloat, B, "u");
+    p.u = u->data_ptr<float>();
+  } else {
+    TORCH_CHECK(given(seed) && given(positions), "sample_tokens: without u, seed and positions are needed");
+    check_vec(*seed, at::kLong, 1, "seed");
+    p.seed = (const long*)seed->data_ptr<int64_t>();
+  }
+  if (given(positions)) {
+    check_vec(*positions, at::kInt, B, "positions");
+    p.positions = positions->data_ptr<int>();
+  }
+  c10::hip::HIPGuardMasqueradingAsCUDA g(dev);
+  Tensor y;
+  if (given(out)) {
+    y = *out;
+    TORCH_CHECK(y.is_cuda() && y.device() == dev && y.scalar_type() == at::kLong, "sample_tokens: out must be int64 on the logits' device");
+    TORCH_CHECK((y.dim() == 1 || (y.dim() == 2 && y.size(1) == 1)) && y.size(0) == B, "sample_tokens: out must be (B,) or (B, 1)");
+  } else {
+    y = at::empty({B, 1}, logits.options().dtype(at::kLong));
+  }
+  if (given(history)) {
+    const Tensor& h = *history;
+    TORCH_CHECK(given(positions), "sample_tokens: history needs positions");
+    TORCH_CHECK(h.is_cuda() && h.device() == dev && h.scalar_type() == at::kLong, "sample_tokens: history must be int64 on the logits' device");
+    TORCH_CHECK(h.dim() == 2 && h.size(0) == B && h.size(1) >= 1 && h.size(1) < (1LL << 31) && h.stride(1) == 1,
+                "sample_tokens: history must be (B, L) with unit inner stride");
+    p.history = (long*)h.data_ptr<int64_t>();
+    p.history_rs = h.stride(0);
+    p.L = (int)h.size(1);
+  }
+  if (given(u_out)) {
+    check_vec(*u_out, at::kFloat, B, "u_out");
+    p.u_out = u_out->data_ptr<float>();
+  }
+  p.logits = (const unsigned short*)logits.data_ptr();
+  p.params = params.data_ptr<int>();
+  p.out_tokens = (long*)y.data_ptr<int64_t>();
+  p.logits_rs = logits.stride(0);
+  p.out_s = y.stride(0);
+  p.B = (int)B; p.V = (int)V;
+  check_launch(orion_sample_tokens(p, cur_stream()), "sample_tokens");
+  return y;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(orion_amd, m) {
@@ -1332,6 +1404,7 @@ TORCH_LIBRARY(orion_amd, m) {
   m.def("attn_decode(Tensor q, Tensor k_cache, Tensor v_cache, Tensor kv_lens, float scale, int splits=0) -> Tensor");
   m.def("kv_append(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor kv_lens, Tensor? q=None, Tensor? cos=None, Tensor? sin=None) -> Tensor");
   m.def("linear_decode(Tensor x, Tensor w, Tensor? bias, int norm, Tensor? norm_w, Tensor? norm_b, float eps, int act, Tensor? residual, Tensor(a!)? out=None) -> Tensor");
+  m.def("sample_tokens(Tensor logits, Tensor params, Tensor? u, Tensor? seed, Tensor? positions, Tensor(a!)? out=None, Tensor(b!)? history=None, Tensor(c!)? u_out=None) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(orion_amd, CUDA, m) {
@@ -1372,4 +1445,5 @@ TORCH_LIBRARY_IMPL(orion_amd, CUDA, m) {
   m.impl("attn_decode", &attn_decode);
   m.impl("kv_append", &kv_append);
   m.impl("linear_decode", &linear_decode);
+  m.impl("sample_tokens", &sample_tokens);
 }

@@ -44,10 +44,19 @@ class DecodeSession:
     per row and returns the logits buffer, which the next step overwrites.  With ``graph=True`` on
     the GPU the first ``step`` warms up on a side stream and captures the step on a single stream
     (a linear chain of in-tree kernels: no library GEMM is inside); every later ``step`` copies
-    the tokens in and replays.  ``captures`` is 0 or 1, ``replays`` counts the replays;
-    :meth:`reset` empties the cache and keeps the graph."""
+    the tokens in and replays.  ``captures`` counts the graphs captured, ``replays`` the replays;
+    :meth:`reset` empties the cache and keeps the graphs.
 
-    def __init__(self, model, batch, max_len=None, graph=False):
+    ``sampler="device"`` makes :meth:`generate` draw the tokens with ``ops.sample_tokens`` on the
+    device: the session then owns ``rng_seed`` (1,) int64, ``sample_params`` (2,) int32
+    (temperature bits, top-k) and ``history`` (batch, max_len + 1) int64, and with ``graph=True``
+    a second graph, the step followed by the sampling launch, that writes each new token into
+    ``tokens`` for the next replay.  ``step`` and its step-only graph do not change; a session
+    holds at most one graph of each kind."""
+
+    def __init__(self, model, batch, max_len=None, graph=False, sampler="torch"):
+        if sampler not in ("torch", "device"):
+            raise ValueError(f"sampler must be 'torch' or 'device', got {sampler!r}")
         cfg = model.config
         self.model = model
         self.is_gpt = hasattr(model, "transformer")
@@ -76,6 +85,14 @@ class DecodeSession:
         self.captures = 0
         self.replays = 0
         self._graph = None
+        self.sampler = sampler
+        self.rng_seed = self.sample_params = self.history = None
+        self._sample_graph = None
+        if sampler == "device":
+            from ..ops.decode import sample_params
+            self.rng_seed = torch.zeros(1, dtype=torch.int64, device=w.device)
+            self.sample_params = sample_params(1.0, None, w.device)
+            self.history = torch.zeros(self.batch, self.max_len + 1, dtype=torch.long, device=w.device)
 
     # ------------------------------------------------------------------ prompt
     @torch.no_grad()
@@ -172,7 +189,7 @@ class DecodeSession:
             with torch.cuda.graph(g):
                 self._body()
             self._graph = g
-            self.captures = 1
+            self.captures += 1
             g.replay()
         cache.pos += 1
         return self.logits
@@ -181,8 +198,11 @@ class DecodeSession:
     @torch.no_grad()
     def generate(self, idx, n, temperature=1.0, top_k=None):
         """Prefill ``idx`` (B, T) and sample ``n`` tokens (T + n - 1 <= max_len): (B, T + n).
-        Sampling stays outside the captured step, on the static logits, and the new tokens go
-        into a preallocated output."""
+        With the default sampler, sampling stays outside the captured step, on the static logits,
+        and the new tokens go into a preallocated output; ``sampler="device"`` is
+        :meth:`_generate_device`."""
+        if self.sampler == "device":
+            return self._generate_device(idx, n, temperature, top_k)
         B, T = idx.shape
         out = torch.empty(B, T + n, dtype=idx.dtype, device=idx.device)
         out[:, :T] = idx
@@ -193,6 +213,75 @@ class DecodeSession:
             if i + 1 < n:
                 logits = self.step(nxt)
         return out
+
+
+    # ------------------------------------------------------------------ sampling on the device
+    def _sample(self, logits):
+        """``ops.sample_tokens`` on device state only: the token of every row of ``logits`` at
+        position ``cache.lens`` goes into ``self.tokens`` and into ``self.history`` at that column."""
+        ops.sample_tokens(logits, params=self.sample_params, seed=self.rng_seed, positions=self.cache.lens,
+                          out=self.tokens, history=self.history)
+
+    def _body_sample(self):
+        self._body()
+        self._sample(self.logits)
+
+    def _step_sample(self):
+        """One decode step on ``self.tokens`` and the draw of the next token into it.  With
+        ``graph=True`` the pair is one captured linear chain; every replay, the capturing call's
+        included, counts in ``replays``."""
+        cache = self.cache
+        if cache.pos + 1 > cache.max_len:
+            raise ValueError(f"KVCache overflow: {cache.pos} cached + 1 new tokens > max_len {cache.max_len}")
+        if not (self.graph and self.on_gpu):
+            self._body_sample()
+        else:
+            if self._sample_graph is None:
+                # as in step(): an eager warm-up on a side stream, the state it advanced or
+                # overwrote (lengths, token) put back, then the capture on one stream; the
+                # history column the warm-up wrote is the one the first replay writes again
+                lens, start, tokens = cache.lens.clone(), cache.start.clone(), self.tokens.clone()
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    self._body_sample()
+                torch.cuda.current_stream().wait_stream(side)
+                cache.lens.copy_(lens)
+                cache.start.copy_(start)
+                self.tokens.copy_(tokens)
+                g = torch.cuda.CUDAGraph()
+                torch.cuda.synchronize()
+                with torch.cuda.graph(g):
+                    self._body_sample()
+                self._sample_graph = g
+                self.captures += 1
+            self._sample_graph.replay()
+            self.replays += 1
+        cache.pos += 1
+
+    def _generate_device(self, idx, n, temperature, top_k):
+        """:meth:`generate` with every draw on the device.  A fresh 64-bit seed from torch's
+        default CPU generator (so ``torch.manual_seed`` governs the tokens) and the sampling
+        parameters are written to the device, the prompt is prefilled and the first token drawn
+        from its logits; the other n - 1 tokens are n - 1 runs of [step, draw] -- replays of one
+        graph with ``graph=True``, with no torch op and no host synchronisation between them.
+        Row b's token at sequence position p uses the uniform of Philox counter (p, b, 0, 0); the
+        tokens are copied out of ``history`` once at the end."""
+        from ..ops.decode import sample_params
+        B, T = idx.shape
+        p0 = self.cache.pos + T  # the first new token's position (a chunked prompt may precede idx)
+        if n < 1:
+            return idx.clone()
+        if p0 + n - 1 > self.max_len:  # before the generator or any session state is touched
+            raise ValueError(f"KVCache overflow: {p0} prompt + {n} - 1 new tokens > max_len {self.max_len}")
+        seed = torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64)
+        self.rng_seed.copy_(seed)
+        sample_params(temperature, top_k, out=self.sample_params)
+        logits = self.prefill(idx)
+        self._sample(logits)
+        for _ in range(n - 1):
+            self._step_sample()
+        return torch.cat((idx, self.history[:, p0:p0 + n].to(idx.dtype)), dim=1)
 
 
 def sample_logits(logits, temperature=1.0, top_k=None):

@@ -175,10 +175,11 @@ class Llama(nn.Module):
         return KVCache(cfg.n_layers, batch, min(max_len or cfg.max_seq_len, cfg.max_seq_len), cfg.n_kv_heads,
                        cfg.head_dim, device=w.device, dtype=w.dtype)
 
-    def decode_session(self, batch, max_len=None, graph=False):
-        """A :class:`DecodeSession` for this model: the fused decode step, captured when ``graph``."""
+    def decode_session(self, batch, max_len=None, graph=False, sampler="torch"):
+        """A :class:`DecodeSession` for this model: the fused decode step, captured when ``graph``;
+        ``sampler="device"`` draws the tokens with ``ops.sample_tokens`` inside that step."""
         from .decode_session import DecodeSession
-        return DecodeSession(self, batch, max_len, graph=graph)
+        return DecodeSession(self, batch, max_len, graph=graph, sampler=sampler)
 
     @torch.no_grad()
     def forward_cached(self, idx, cache):
@@ -214,18 +215,26 @@ class Llama(nn.Module):
         return ops.linear(h[:, -1, :].contiguous(), self.lm_head.weight)
 
     @torch.no_grad()
-    def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, use_cache=False):
+    def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, use_cache=False, sampler="torch"):
         """Sampling loop.  ``use_cache=True`` keeps every layer's keys / values
         (:class:`KVCache`): the prompt is prefilled once and each new token costs one single-token
         forward; tokens beyond ``max_seq_len`` take the uncached sliding-window loop below.
         ``use_cache="fused"`` runs the cached tokens through a :class:`DecodeSession` (the fused
         skinny-linear decode step), ``"graph"`` additionally replays that step from one captured
-        HIP graph."""
+        HIP graph.  With either, ``sampler="device"`` draws the session's tokens with
+        ``ops.sample_tokens`` inside the step (seeded from torch's default generator) instead of
+        stock torch ops between the steps."""
         if isinstance(use_cache, str) and use_cache not in ("fused", "graph"):
             raise ValueError(f"use_cache must be False, True, 'fused' or 'graph', got {use_cache!r}")
+        if sampler not in ("torch", "device"):
+            raise ValueError(f"sampler must be 'torch' or 'device', got {sampler!r}")
+        if sampler == "device" and not isinstance(use_cache, str):
+            raise ValueError("sampler='device' samples inside the fused decode step: use_cache must be 'fused' "
+                             f"or 'graph', got {use_cache!r}")
         if isinstance(use_cache, str) and max_new_tokens > 0 and idx.size(1) < self.config.max_seq_len:
             n = min(max_new_tokens, self.config.max_seq_len - idx.size(1) + 1)
-            sess = self.decode_session(idx.size(0), idx.size(1) + n - 1, graph=use_cache == "graph")
+            sess = self.decode_session(idx.size(0), idx.size(1) + n - 1, graph=use_cache == "graph",
+                                       sampler=sampler)
             idx = sess.generate(idx, n, temperature, top_k)
             max_new_tokens -= n
         elif use_cache and max_new_tokens > 0 and idx.size(1) < self.config.max_seq_len:

@@ -405,6 +405,62 @@ def linear_decode(x, weight, bias=None, *, norm=None, norm_weight=None, norm_bia
     return out.view(y.shape)
 
 
+def sample_tokens_eligible(logits):
+    """Whether the sampling kernel (csrc/sample.hip) takes these logits on the HIP backend:
+    (B, V) bf16 on the GPU with unit stride on V."""
+    if not logits.is_cuda or _BACKEND != "hip":
+        return False
+    from .decode import sample_tokens_eligible as ok
+    return ok(logits)
+
+
+def sample_tokens(logits, temperature=1.0, top_k=None, *, u=None, seed=None, positions=None, out=None,
+                  history=None, params=None, u_out=None):
+    """One token per row of logits (B, V) -> (B, 1) int64 by the models' sampling rule with an
+    explicit uniform: z = logits / max(temperature, 1e-6); with ``top_k`` only the entries >= the
+    k-th largest of the row are kept (ties at the threshold all stay; None, <= 0 or >= V keeps
+    everything); w = exp(z - max z) over the kept entries, and the token is the first kept index
+    whose running sum in index order exceeds u sum(w) (the last kept index if rounding leaves
+    none).  ``u`` (B,) fp32 is given, or is ``ref.philox_uniform(seed, positions)``: Philox4x32-10
+    keyed by the 64-bit ``seed`` (an int or a (1,) int64 tensor) at counter (positions[b], b, 0, 0),
+    ``positions`` (B,) int32, so no generator state is advanced.  ``out`` (B,) or (B, 1) int64
+    takes the token in place, ``history`` (B, L) int64 also gets it at column positions[b] (skipped
+    when that is >= L) and ``u_out`` (B,) fp32 the u that was used.
+
+    On the GPU one launch when :func:`sample_tokens_eligible` (bf16 on the HIP backend), reading
+    the temperature and top_k from ``params`` (``ops.decode.sample_params``; built from the two
+    arguments when not given), so a captured launch serves every setting; other GPU inputs take
+    the same rule on stock ops in fp32 (top-k mask, cumsum, searchsorted) and CPU tensors the fp64
+    reference.  Inference only."""
+    from .decode import _no_grad
+    _no_grad(logits)
+    assert logits.dim() == 2, "sample_tokens: logits must be (B, V)"
+    b = _gpu(logits)
+    if b == "hip" and sample_tokens_eligible(logits):
+        from .decode import sample_params, sample_tokens_hip
+        if params is None:
+            params = sample_params(temperature, top_k, logits.device)
+        if u is None and seed is not None and not isinstance(seed, torch.Tensor):
+            seed = torch.tensor([_wrap_i64(seed)], dtype=torch.int64).to(logits.device)
+        return sample_tokens_hip(logits, params, u, seed, positions, out, history, u_out)
+    if params is not None:
+        from .decode import read_sample_params
+        temperature, top_k = read_sample_params(params)
+    if u is None:
+        assert seed is not None and positions is not None, "sample_tokens: without u, seed and positions are needed"
+        u = ref.philox_uniform(seed, positions)
+    if u_out is not None:
+        u_out.copy_(u)
+    return ref.sample_tokens(logits, temperature, top_k, u, None, positions, out, history,
+                             dtype=torch.float64 if b is None else torch.float32)
+
+
+def _wrap_i64(v):
+    """A 64-bit pattern given as any Python int, as the int64 that holds it."""
+    v = int(v) & ((1 << 64) - 1)
+    return v - (1 << 64) if v >= 1 << 63 else v
+
+
 # --------------------------------------------------------------------------- loss
 def cross_entropy(logits, targets, ignore_index=-1):
     b = _gpu(logits)
@@ -436,6 +492,7 @@ __all__ = [
     "cross_entropy", "swiglu_mlp", "linear_residual_layer_norm", "mlp_residual_layer_norm",
     "linear_residual_rms_norm", "swiglu_residual_rms_norm",
     "linear_cross_entropy", "attention_decode", "kv_append", "linear_decode", "linear_decode_eligible",
+    "sample_tokens", "sample_tokens_eligible",
 ]
 
 

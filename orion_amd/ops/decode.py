@@ -76,6 +76,42 @@ def kv_append_hip(k_new, v_new, k_cache, v_cache, kv_lens, q=None, cos=None, sin
     return q_rot if q is not None else None
 
 
+def sample_tokens_eligible(logits):
+    """Whether csrc/sample.hip takes these logits: (B, V) bf16 on the GPU with unit stride on V
+    (any row stride, any alignment of the rows)."""
+    return (logits.is_cuda and logits.dtype == torch.bfloat16 and logits.dim() == 2 and logits.numel() > 0
+            and logits.stride(1) == 1 and logits.shape[1] < 2 ** 31)
+
+
+def sample_params(temperature=1.0, top_k=None, device=None, out=None):
+    """The sampling kernel's device-resident parameters: (2,) int32 holding the fp32 bits of the
+    temperature and top_k (0: keep everything).  ``out`` is overwritten in place (a session's
+    buffer, read by its captured launch)."""
+    import struct
+    bits = struct.unpack("<i", struct.pack("<f", float(temperature)))[0]
+    k = 0 if top_k is None else max(0, min(int(top_k), 2 ** 31 - 1))
+    host = torch.tensor([bits, k], dtype=torch.int32)
+    if out is None:
+        return host.to(device)
+    out.copy_(host)
+    return out
+
+
+def read_sample_params(params):
+    """(temperature, top_k) back from a :func:`sample_params` tensor (reads it on the host)."""
+    import struct
+    bits, k = params.tolist()
+    return struct.unpack("<f", struct.pack("<i", bits))[0], (k if k > 0 else None)
+
+
+def sample_tokens_hip(logits, params, u=None, seed=None, positions=None, out=None, history=None, u_out=None):
+    """One launch, one workgroup per row: the token of every row of logits (B, V) -> (B, 1) int64
+    (``out`` when given).  ``params`` from :func:`sample_params`; ``u`` (B,) fp32 or the kernel's
+    own Philox draw from ``seed`` (1,) int64 and ``positions`` (B,) int32, all on the device."""
+    _no_grad(logits)
+    return C().sample_tokens(logits, params, u, seed, positions, out, history, u_out).view(-1, 1)
+
+
 def attention_decode_torch(q, k_cache, v_cache, kv_lens, scale=None):
     """Stock PyTorch: SDPA on each row's valid slice (reads the lengths on the host)."""
     _no_grad(q, k_cache, v_cache)

@@ -166,6 +166,103 @@ def linear_decode(x, weight, bias=None, norm=None, norm_weight=None, norm_bias=N
     return y
 
 
+def philox4x32_10(counter, key):
+    """Philox4x32-10 in integer math: ``counter`` (..., 4) and ``key`` (2,) of 32-bit words (any
+    integer type) -> the four output words, a uint32 array (..., 4).  One round is p0 = 0xD2511F53
+    c0, p1 = 0xCD9E8D57 c2 (64-bit products), c <- (hi(p1) ^ c1 ^ k0, lo(p1), hi(p0) ^ c3 ^ k1,
+    lo(p0)), then k0 += 0x9E3779B9, k1 += 0xBB67AE85."""
+    import numpy as np
+    m32 = np.uint64(0xFFFFFFFF)
+    c = np.asarray(counter).astype(np.uint64) & m32
+    c0, c1, c2, c3 = (c[..., i].copy() for i in range(4))
+    k = [int(v) & 0xFFFFFFFF for v in np.asarray(key).reshape(2).tolist()]
+    k0, k1 = k
+    for _ in range(10):
+        p0 = (np.uint64(0xD2511F53) * c0)  # < 2^64: both factors are below 2^32
+        p1 = (np.uint64(0xCD9E8D57) * c2)
+        c0, c1, c2, c3 = ((p1 >> np.uint64(32)) ^ c1 ^ np.uint64(k0), p1 & m32,
+                          (p0 >> np.uint64(32)) ^ c3 ^ np.uint64(k1), p0 & m32)
+        k0 = (k0 + 0x9E3779B9) & 0xFFFFFFFF
+        k1 = (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def uniform_from_word(x0):
+    """A 32-bit word (uint32 array) -> fp32 u = (x0 >> 8) 2^-24 + 2^-25, rounded to fp32 and capped
+    at 1 - 2^-24 (the sum of the largest word is a tie that rounds up to 1.0): strictly inside
+    (0, 1)."""
+    import numpy as np
+    u = (np.asarray(x0, dtype=np.uint32) >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    return np.minimum(u + np.float32(2.0 ** -25), np.float32(1.0 - 2.0 ** -24))
+
+
+def philox_uniform(seed, positions):
+    """The sampling kernel's uniforms, bit for bit: row b draws word 0 of Philox4x32-10 with the
+    two 32-bit halves of the 64-bit ``seed`` (an int or a one-element tensor) as key and
+    (positions[b], b, 0, 0) as counter; u = :func:`uniform_from_word` of it, strictly inside (0, 1).
+    ``positions`` (B,) integer tensor -> (B,) fp32 on its device."""
+    import numpy as np
+    seed = int(seed.reshape(-1)[0].item()) if isinstance(seed, torch.Tensor) else int(seed)
+    seed &= (1 << 64) - 1
+    pos = positions.detach().cpu().numpy().astype(np.int64)
+    ctr = np.zeros((pos.shape[0], 4), dtype=np.int64)
+    ctr[:, 0] = pos & 0xFFFFFFFF
+    ctr[:, 1] = np.arange(pos.shape[0])
+    x0 = philox4x32_10(ctr, (seed & 0xFFFFFFFF, seed >> 32))[:, 0]
+    return torch.from_numpy(uniform_from_word(x0)).to(positions.device)
+
+
+def sample_keep_mask(logits, top_k=None):
+    """The entries the sampling rule keeps: every one >= the top_k-th largest of its row, ties at
+    the threshold included; all of them for top_k None, <= 0 or >= V."""
+    V = logits.size(-1)
+    if top_k is None or top_k <= 0 or top_k >= V:
+        return torch.ones_like(logits, dtype=torch.bool)
+    v, _ = torch.topk(logits.float(), int(top_k))
+    return ~(logits.float() < v[:, [-1]])
+
+
+def sample_cdf(logits, temperature=1.0, top_k=None, dtype=torch.float64):
+    """Running sums in index order of w = exp(z - max z) over the kept entries of logits (B, V),
+    z = logits / max(temperature, 1e-6), and their total Z: ((B, V), (B, 1)) in ``dtype``."""
+    keep = sample_keep_mask(logits, top_k)
+    z = logits.to(dtype) / max(float(temperature), 1e-6)
+    z = z.masked_fill(~keep, -float("inf"))
+    w = torch.exp(z - z.max(dim=-1, keepdim=True).values).masked_fill(~keep, 0.0)
+    c = torch.cumsum(w, dim=-1)
+    return c, c[:, -1:]
+
+
+def sample_tokens(logits, temperature=1.0, top_k=None, u=None, seed=None, positions=None, out=None, history=None,
+                  dtype=torch.float64):
+    """The models' sampling rule with an explicit uniform per row: the token of row b is the first
+    kept index whose running sum (:func:`sample_cdf`, fp64) exceeds u[b] Z, or the last kept
+    index if rounding leaves none.  ``u`` (B,) is given or is :func:`philox_uniform` of ``seed``
+    and ``positions``.  Returns (B, 1) int64 (``out`` (B,) or (B, 1) when given); with ``history``
+    (B, L) the token also goes to history[b, positions[b]] unless the position is >= L."""
+    B, V = logits.shape
+    if u is None:
+        assert seed is not None and positions is not None, "without u, seed and positions are needed"
+        u = philox_uniform(seed, positions)
+    c, Z = sample_cdf(logits, temperature, top_k, dtype)
+    tok = torch.searchsorted(c, u.to(device=c.device, dtype=dtype).view(B, 1) * Z, right=True)
+    keep = sample_keep_mask(logits, top_k)
+    last = (keep * torch.arange(V, device=logits.device)).max(dim=-1, keepdim=True).values
+    tok = torch.where(tok >= V, last, tok).clamp_(0, V - 1)
+    if out is None:
+        out = tok
+    else:
+        out.view(B, 1).copy_(tok)
+        out = out.view(B, 1)
+    if history is not None:
+        assert positions is not None, "history needs positions"
+        pos = positions.long()
+        ok = (pos >= 0) & (pos < history.size(1))
+        rows = torch.arange(B, device=history.device)[ok]
+        history[rows, pos[ok]] = tok[ok, 0]
+    return out
+
+
 def cross_entropy(logits, targets, ignore_index=-1):
     return F.cross_entropy(logits.float(), targets, ignore_index=ignore_index)
 

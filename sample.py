@@ -9,7 +9,9 @@ available), ``FILE:<path>``, or a comma-separated list of token ids
 ``--kv_cache=True`` generates through the key/value cache (one single-token forward per new
 token, ``generate(use_cache=True)``) instead of re-running the whole prefix; ``--kv_cache=fused``
 runs those tokens on the fused decode step and ``--kv_cache=graph`` replays that step from one
-captured HIP graph (``generate(use_cache="fused" / "graph")``).
+captured HIP graph (``generate(use_cache="fused" / "graph")``).  ``--sampler=device`` (with
+``fused`` or ``graph``) draws the tokens with the sampling kernel inside that step instead of stock
+torch ops between the steps (``generate(..., sampler="device")``).
 """
 from __future__ import annotations
 
@@ -22,7 +24,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 DEFAULTS = dict(out_dir="out", start="\n", num_samples=10, max_new_tokens=500, temperature=0.8,
-                top_k=200, seed=1337, device="cuda", ckpt="ckpt.pt", kv_cache=False)
+                top_k=200, seed=1337, device="cuda", ckpt="ckpt.pt", kv_cache=False, sampler="torch")
 
 
 def main(argv=None):
@@ -65,10 +67,12 @@ def main(argv=None):
     kv = cfg["kv_cache"]
     if isinstance(kv, str) and kv not in ("fused", "graph"):
         raise ValueError(f"--kv_cache must be True, False, fused or graph, got {kv!r}")
+    if cfg["sampler"] not in ("torch", "device"):
+        raise ValueError(f"--sampler must be torch or device, got {cfg['sampler']!r}")
     with torch.no_grad():
         for _ in range(cfg["num_samples"]):
             y = model.generate(x, cfg["max_new_tokens"], temperature=cfg["temperature"], top_k=cfg["top_k"],
-                               use_cache=kv if kv in ("fused", "graph") else bool(kv))
+                               use_cache=kv if kv in ("fused", "graph") else bool(kv), sampler=cfg["sampler"])
             toks = y[0].tolist()
             print(decode(toks) if decode else toks)
             print("---------------")

@@ -3,17 +3,19 @@
 torch SDPA on the same cache view, at the GPT-2 and the Llama-GQA decode shapes; (ii) generated
 tokens/s of ``gpt2`` with and without the KV cache (prompt 64 + 256 new tokens at B 1 and 8, and
 a long-context point, prompt 768 at B 8) and on the fused decode step, eager (``fused``) and
-replayed from one captured HIP graph (``graph``), the arms alternating; (iii) the skinny decode
+replayed from one captured HIP graph (``graph``) and with the tokens drawn inside that graph
+(``graph_device``: ``sampler="device"``), the arms alternating; (iii) the skinny decode
 linear (csrc/linear_decode.hip) at every projection shape of ``gpt2`` and of the Llama-2-7B layer
 at M = 1, 8, 16 beside the same call through ``F.linear`` with its separate norm / activation /
-residual launches.
+residual launches; (iv) the sampling kernel (csrc/sample.hip) beside ``sample_logits`` (stock
+torch ops) on the same logits at B 1, 8, 16 and V 50,304 and 32,000, top-k 200 and none.
 
 The kernel timing rotates over enough distinct caches to exceed the 256 MB Infinity Cache, so
 every call streams its K and V from HBM; bytes/s counts the K + V actually read (one pass per
 KV head); the linear timing rotates over weights the same way and counts the weight bytes.
 Prints one JSON line per measurement.
 
-usage: python scripts/bench_decode.py [--kernel 0|1] [--linear 0|1] [--generate 0|1] [--rounds N]
+usage: python scripts/bench_decode.py [--kernel 0|1] [--linear 0|1] [--sample 0|1] [--generate 0|1] [--rounds N]
 """
 import argparse
 import json
@@ -144,6 +146,33 @@ def bench_linear(model, name, N, K, norm, act, bias, residual, M, rounds):
     print(json.dumps(out), flush=True)
 
 
+def bench_sample(B, V, top_k, rounds):
+    """Device time of one ``ops.sample_tokens`` launch beside ``sample_logits`` on the same logits
+    (rotating over 8 logits buffers; both draw their own random numbers)."""
+    from orion_amd.models.decode_session import sample_logits
+    from orion_amd.ops.decode import sample_params
+    g = torch.Generator(device="cuda").manual_seed(0)
+    logits = [(torch.randn(B, V, device="cuda", generator=g) * 2.5).to(torch.bfloat16) for _ in range(8)]
+    params = sample_params(0.8, top_k, "cuda")
+    seed = torch.tensor([1234], dtype=torch.int64, device="cuda")
+    pos = torch.arange(B, dtype=torch.int32, device="cuda")
+    out = torch.zeros(B, 1, dtype=torch.long, device="cuda")
+
+    def hip(i):
+        return ops.sample_tokens(logits[i % 8], params=params, seed=seed, positions=pos, out=out)
+
+    def stock(i):
+        return sample_logits(logits[i % 8], 0.8, top_k)
+
+    assert ops.sample_tokens_eligible(logits[0])
+    us = _time_us({"hip": hip, "sample_logits": stock}, rounds)
+    res = dict(bench="sample_tokens", B=B, V=V, top_k=top_k, temperature=0.8)
+    for k, v in us.items():
+        res[f"{k}_us"] = round(v, 2)
+    res["speedup"] = round(us["sample_logits"] / us["hip"], 2)
+    print(json.dumps(res), flush=True)
+
+
 def bench_graph_steady(model, B, prompt_len, new_tokens):
     """The graph arm without its capture: per-token time of the sampling loop on a captured
     session, and of the replay alone (the rest is the sampling launches)."""
@@ -174,16 +203,17 @@ def bench_generate(B, prompt_len, new_tokens, rounds):
     torch.manual_seed(0)
     model = build_gpt2("gpt2").to("cuda").to(torch.bfloat16).eval()
     prompt = torch.randint(0, 50257, (B, prompt_len), device="cuda")
-    arms = {"cached": True, "uncached": False, "fused": "fused", "graph": "graph"}
-    for use_cache in arms.values():  # warm-up: every shape of both arms
-        model.generate(prompt, new_tokens, top_k=200, use_cache=use_cache)
+    arms = {"cached": dict(use_cache=True), "uncached": dict(use_cache=False), "fused": dict(use_cache="fused"),
+            "graph": dict(use_cache="graph"), "graph_device": dict(use_cache="graph", sampler="device")}
+    for kw in arms.values():  # warm-up: every shape of every arm
+        model.generate(prompt, new_tokens, top_k=200, **kw)
     torch.cuda.synchronize()
     ts = {k: [] for k in arms}
     for _ in range(rounds):
-        for name, use_cache in arms.items():
+        for name, kw in arms.items():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            out = model.generate(prompt, new_tokens, top_k=200, use_cache=use_cache)
+            out = model.generate(prompt, new_tokens, top_k=200, **kw)
             torch.cuda.synchronize()
             ts[name].append(time.perf_counter() - t0)
             assert out.shape == (B, prompt_len + new_tokens)
@@ -196,6 +226,7 @@ def bench_generate(B, prompt_len, new_tokens, rounds):
     best = min(med["cached"], med["uncached"])  # the faster of the two arms that predate the fused step
     res["fused_over_best_baseline"] = round(best / med["fused"], 2)
     res["graph_over_best_baseline"] = round(best / med["graph"], 2)
+    res["graph_device_over_graph"] = round(med["graph"] / med["graph_device"], 2)
     steady = bench_graph_steady(model, B, prompt_len, new_tokens)
     res["graph_steady_ms_per_token"] = round(steady["token"] * 1e3, 3)
     res["graph_replay_ms_per_token"] = round(steady["replay"] * 1e3, 3)
@@ -207,6 +238,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--kernel", type=int, default=1)
     ap.add_argument("--linear", type=int, default=1)
+    ap.add_argument("--sample", type=int, default=1)
     ap.add_argument("--generate", type=int, default=1)
     ap.add_argument("--rounds", type=int, default=5)
     a = ap.parse_args()
@@ -222,6 +254,11 @@ def main():
                 for shape in shapes:
                     for M in (1, 8, 16):
                         bench_linear(model, *shape, M=M, rounds=max(a.rounds, 5))
+        if a.sample:
+            for V in (50304, 32000):
+                for B in (1, 8, 16):
+                    for top_k in (200, None):
+                        bench_sample(B, V, top_k, rounds=max(a.rounds, 5))
         if a.generate:
             for B in (1, 8):
                 bench_generate(B, 64, 256, a.rounds)
