@@ -13,32 +13,16 @@ on the session's cache and is never captured.
 from __future__ import annotations
 
 import torch
-import torch.nn.functional as F
 
 from .. import ops
 from ..ops.decode import MAX_ROWS as MAX_GRAPH_BATCH  # rows of ops.linear_decode's kernel
-
-
-def _projections(model):
-    """(name, weight) of every projection of the decode step."""
-    if hasattr(model, "transformer"):
-        for i, blk in enumerate(model.transformer.h):
-            yield f"h.{i}.attn.c_attn", blk.attn.c_attn.weight
-            yield f"h.{i}.attn.c_proj", blk.attn.c_proj.weight
-            yield f"h.{i}.mlp.c_fc", blk.mlp.c_fc.weight
-            yield f"h.{i}.mlp.c_proj", blk.mlp.c_proj.weight
-    else:
-        for i, layer in enumerate(model.layers):
-            yield f"layers.{i}.self_attn.qkv_proj", layer.self_attn.qkv_proj.weight
-            yield f"layers.{i}.self_attn.o_proj", layer.self_attn.o_proj.weight
-            yield f"layers.{i}.mlp.gate_up_proj", layer.mlp.gate_up_proj.weight
-            yield f"layers.{i}.mlp.down_proj", layer.mlp.down_proj.weight
-    yield "lm_head", model.lm_head.weight
+from . import generation
 
 
 class DecodeSession:
     """One key/value cache, a static (B, 1) token buffer and a static (B, vocab) logits buffer for
-    a :class:`GPT` or :class:`Llama` model.
+    a model that has ``new_cache``, ``forward_cached``, ``decode_step`` and ``decode_projections``
+    (:class:`GPT`, :class:`Llama`).
 
     ``prefill(idx)`` feeds a prompt (in one or several chunks); ``step(tokens)`` appends one token
     per row and returns the logits buffer, which the next step overwrites.  With ``graph=True`` on
@@ -59,10 +43,7 @@ class DecodeSession:
             raise ValueError(f"sampler must be 'torch' or 'device', got {sampler!r}")
         cfg = model.config
         self.model = model
-        self.is_gpt = hasattr(model, "transformer")
-        limit = cfg.block_size if self.is_gpt else cfg.max_seq_len
         self.batch = int(batch)
-        self.max_len = min(int(max_len or limit), limit)
         w = model.lm_head.weight
         self.on_gpu = w.is_cuda
         self.graph = bool(graph)
@@ -71,7 +52,7 @@ class DecodeSession:
                 raise ValueError(f"DecodeSession(graph=True): batch {self.batch} > {MAX_GRAPH_BATCH}, the most "
                                  "rows the skinny linear kernel takes")
             probes = {}  # one input of the step's shape per K
-            for name, pw in _projections(model):
+            for name, pw in model.decode_projections():
                 K = pw.shape[1]
                 if K not in probes:
                     probes[K] = torch.empty(self.batch, K, device=w.device, dtype=w.dtype)
@@ -79,7 +60,8 @@ class DecodeSession:
                     raise ValueError(f"DecodeSession(graph=True): {name} {tuple(pw.shape)} {pw.dtype} is not "
                                      "eligible for ops.linear_decode (bf16 on the HIP backend, K % 8 == 0, "
                                      "contiguous weight), and a library GEMM must not be captured")
-        self.cache = model.new_cache(self.batch, self.max_len)
+        self.cache = model.new_cache(self.batch, max_len)  # at most the model's context limit
+        self.max_len = self.cache.max_len
         self.tokens = torch.zeros(self.batch, 1, dtype=torch.long, device=w.device)
         self.logits = torch.zeros(self.batch, cfg.vocab_size, dtype=w.dtype, device=w.device)
         self.captures = 0
@@ -112,60 +94,35 @@ class DecodeSession:
         cache = self.cache
         cache.start.copy_(cache.lens)
         cache.lens.add_(1)
-        if self.is_gpt:
-            self._gpt_body()
-        else:
-            self._llama_body()
+        self.model.decode_step(self.tokens, cache, self.logits)
 
-    def _gpt_body(self):
-        m, cache, B = self.model, self.cache, self.batch
-        cfg, tr = m.config, m.transformer
-        H, D = cfg.n_head, cfg.head_dim
-        x = F.embedding(self.tokens[:, 0], tr.wte.weight) + F.embedding(cache.start, tr.wpe.weight)
-        for i, blk in enumerate(tr.h):
-            at, ml = blk.attn, blk.mlp
-            qkv = ops.linear_decode(x, at.c_attn.weight, at.c_attn.bias, norm="layer", norm_weight=blk.ln_1.weight,
-                                    norm_bias=blk.ln_1.bias).view(B, 1, 3, H, D)
-            kc, vc = cache.layer(i)
-            ops.kv_append(qkv[:, :, 1], qkv[:, :, 2], kc, vc, cache.start)
-            # the whole cache view: the key split is planned from max_len once and never changes
-            y = ops.attention_decode(qkv[:, 0, 0], kc, vc, cache.lens)
-            x = ops.linear_decode(y.view(B, H * D), at.c_proj.weight, at.c_proj.bias, residual=x)
-            h = ops.linear_decode(x, ml.c_fc.weight, ml.c_fc.bias, norm="layer", norm_weight=blk.ln_2.weight,
-                                  norm_bias=blk.ln_2.bias, act="gelu")
-            x = ops.linear_decode(h, ml.c_proj.weight, ml.c_proj.bias, residual=x)
-        ops.linear_decode(x, m.lm_head.weight, norm="layer", norm_weight=tr.ln_f.weight, norm_bias=tr.ln_f.bias,
-                          out=self.logits)
-
-    def _llama_body(self):
-        m, cache, B = self.model, self.cache, self.batch
-        cfg = m.config
-        Hq, Hkv, D = cfg.n_heads, cfg.n_kv_heads, cfg.head_dim
-        cos, sin = m.rope_cos, m.rope_sin
-        x = F.embedding(self.tokens[:, 0], m.embed_tokens.weight)
-        for i, layer in enumerate(m.layers):
-            at, ff = layer.self_attn, layer.mlp
-            ln1, ln2 = layer.input_layernorm, layer.post_attention_layernorm
-            qkv = ops.linear_decode(x, at.qkv_proj.weight, norm="rms", norm_weight=ln1.weight,
-                                    eps=ln1.eps).view(B, 1, Hq + 2 * Hkv, D)
-            kc, vc = cache.layer(i)
-            q = ops.kv_append(qkv[:, :, Hq:Hq + Hkv], qkv[:, :, Hq + Hkv:], kc, vc, cache.start,
-                              q=qkv[:, :, :Hq], cos=cos, sin=sin)
-            y = ops.attention_decode(q[:, 0], kc, vc, cache.lens)
-            x = ops.linear_decode(y.view(B, Hq * D), at.o_proj.weight, residual=x)
-            h = ops.linear_decode(x, ff.gate_up_proj.weight, norm="rms", norm_weight=ln2.weight, eps=ln2.eps,
-                                  act="swiglu")
-            x = ops.linear_decode(h, ff.down_proj.weight, residual=x)
-        ops.linear_decode(x, m.lm_head.weight, norm="rms", norm_weight=m.norm.weight, eps=m.norm.eps,
-                          out=self.logits)
+    def _capture(self, body, restore):
+        """``body`` as a graph.  An eager warm-up on a side stream first (lazy initialisations must
+        not happen inside a capture), then the tensors ``restore`` that it advanced or overwrote
+        put back, then the capture on the current stream.  A capture launches nothing: the
+        caller's first replay is its step."""
+        saved = [t.clone() for t in restore]
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            body()
+        torch.cuda.current_stream().wait_stream(side)
+        for t, s in zip(restore, saved):
+            t.copy_(s)
+        g = torch.cuda.CUDAGraph()
+        torch.cuda.synchronize()
+        with torch.cuda.graph(g):
+            body()
+        self.captures += 1
+        return g
 
     @torch.no_grad()
     def step(self, tokens):
         """Append ``tokens`` (B,) or (B, 1) and return the static logits buffer (B, vocab) of the
-        next position.  Raises ``ValueError`` before any launch when the cache is full."""
+        next position.  Raises ``ValueError`` before any launch when the cache is full.  The
+        capturing call's own replay does not count in ``replays``."""
         cache = self.cache
-        if cache.pos + 1 > cache.max_len:
-            raise ValueError(f"KVCache overflow: {cache.pos} cached + 1 new tokens > max_len {cache.max_len}")
+        cache.check_room(1)
         self.tokens.copy_(tokens.reshape(self.batch, 1))
         if not (self.graph and self.on_gpu):
             self._body()
@@ -173,24 +130,8 @@ class DecodeSession:
             self._graph.replay()
             self.replays += 1
         else:
-            # eager warm-up on a side stream (lazy initialisations must not happen inside a
-            # capture), the lengths put back afterwards; then the capture on one stream.  A capture
-            # launches nothing, so the first replay is this call's step.
-            lens, start = cache.lens.clone(), cache.start.clone()
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._body()
-            torch.cuda.current_stream().wait_stream(side)
-            cache.lens.copy_(lens)
-            cache.start.copy_(start)
-            g = torch.cuda.CUDAGraph()
-            torch.cuda.synchronize()
-            with torch.cuda.graph(g):
-                self._body()
-            self._graph = g
-            self.captures += 1
-            g.replay()
+            self._graph = self._capture(self._body, (cache.lens, cache.start))
+            self._graph.replay()
         cache.pos += 1
         return self.logits
 
@@ -208,12 +149,11 @@ class DecodeSession:
         out[:, :T] = idx
         logits = self.prefill(idx)
         for i in range(n):
-            nxt = sample_logits(logits, temperature, top_k)
+            nxt = generation.sample_logits(logits, temperature, top_k)
             out[:, T + i:T + i + 1] = nxt
             if i + 1 < n:
                 logits = self.step(nxt)
         return out
-
 
     # ------------------------------------------------------------------ sampling on the device
     def _sample(self, logits):
@@ -231,30 +171,13 @@ class DecodeSession:
         ``graph=True`` the pair is one captured linear chain; every replay, the capturing call's
         included, counts in ``replays``."""
         cache = self.cache
-        if cache.pos + 1 > cache.max_len:
-            raise ValueError(f"KVCache overflow: {cache.pos} cached + 1 new tokens > max_len {cache.max_len}")
+        cache.check_room(1)
         if not (self.graph and self.on_gpu):
             self._body_sample()
         else:
             if self._sample_graph is None:
-                # as in step(): an eager warm-up on a side stream, the state it advanced or
-                # overwrote (lengths, token) put back, then the capture on one stream; the
-                # history column the warm-up wrote is the one the first replay writes again
-                lens, start, tokens = cache.lens.clone(), cache.start.clone(), self.tokens.clone()
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    self._body_sample()
-                torch.cuda.current_stream().wait_stream(side)
-                cache.lens.copy_(lens)
-                cache.start.copy_(start)
-                self.tokens.copy_(tokens)
-                g = torch.cuda.CUDAGraph()
-                torch.cuda.synchronize()
-                with torch.cuda.graph(g):
-                    self._body_sample()
-                self._sample_graph = g
-                self.captures += 1
+                # the history column the warm-up wrote is the one the first replay writes again
+                self._sample_graph = self._capture(self._body_sample, (cache.lens, cache.start, self.tokens))
             self._sample_graph.replay()
             self.replays += 1
         cache.pos += 1
@@ -272,8 +195,7 @@ class DecodeSession:
         p0 = self.cache.pos + T  # the first new token's position (a chunked prompt may precede idx)
         if n < 1:
             return idx.clone()
-        if p0 + n - 1 > self.max_len:  # before the generator or any session state is touched
-            raise ValueError(f"KVCache overflow: {p0} prompt + {n} - 1 new tokens > max_len {self.max_len}")
+        self.cache.check_room(T + n - 1)  # before the generator or any session state is touched
         seed = torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64)
         self.rng_seed.copy_(seed)
         sample_params(temperature, top_k, out=self.sample_params)
@@ -282,12 +204,3 @@ class DecodeSession:
         for _ in range(n - 1):
             self._step_sample()
         return torch.cat((idx, self.history[:, p0:p0 + n].to(idx.dtype)), dim=1)
-
-
-def sample_logits(logits, temperature=1.0, top_k=None):
-    """The models' sampling rule on (B, vocab) logits -> (B, 1) token ids."""
-    logits = logits.float() / max(temperature, 1e-6)
-    if top_k is not None:
-        v, _ = torch.topk(logits, min(top_k, logits.size(-1)))
-        logits[logits < v[:, [-1]]] = -float("inf")
-    return torch.multinomial(torch.softmax(logits, dim=-1), num_samples=1)

@@ -1,0 +1,69 @@
+"""What :class:`GPT` and :class:`Llama` share in generation: the sampling rule and the loop that
+hands over from the key/value cache (or a :class:`DecodeSession`) to the sliding window.
+
+A model inherits :class:`Generation` and says what is its own: ``context_len``, ``new_cache``,
+``forward_cached``, and for the fused decode step ``decode_step`` and ``decode_projections``.
+"""
+from __future__ import annotations
+
+import torch
+
+
+def sample_logits(logits, temperature=1.0, top_k=None):
+    """The models' sampling rule on (B, vocab) logits -> (B, 1) token ids: temperature, the top-k
+    threshold (ties kept), softmax, one draw per row from torch's default generator."""
+    logits = logits.float() / max(temperature, 1e-6)
+    if top_k is not None:
+        v, _ = torch.topk(logits, min(top_k, logits.size(-1)))
+        logits[logits < v[:, [-1]]] = -float("inf")
+    return torch.multinomial(torch.softmax(logits, dim=-1), num_samples=1)
+
+
+class Generation:
+    """``generate`` and ``decode_session`` of a model with a :class:`KVCache`."""
+
+    def decode_session(self, batch, max_len=None, graph=False, sampler="torch"):
+        """A :class:`DecodeSession` for this model: the fused decode step, captured when ``graph``;
+        ``sampler="device"`` draws the tokens with ``ops.sample_tokens`` inside that step."""
+        from .decode_session import DecodeSession
+        return DecodeSession(self, batch, max_len, graph=graph, sampler=sampler)
+
+    @torch.no_grad()
+    def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, use_cache=False, sampler="torch"):
+        """nanoGPT's sampling loop.  ``use_cache=True`` keeps every layer's keys / values
+        (:class:`KVCache`): the prompt is prefilled once and each new token costs one single-token
+        forward.  Tokens beyond the context limit (``block_size`` / ``max_seq_len``) take the
+        uncached sliding-window loop below: cropping the window shifts the positions, which
+        invalidates a cache.  ``use_cache="fused"`` runs the cached tokens through a
+        :class:`DecodeSession` (the fused skinny-linear decode step), ``"graph"`` additionally
+        replays that step from one captured HIP graph.  With either, ``sampler="device"`` draws
+        the session's tokens with ``ops.sample_tokens`` inside the step (seeded from torch's
+        default generator) instead of stock torch ops between the steps."""
+        fused = isinstance(use_cache, str)
+        if fused and use_cache not in ("fused", "graph"):
+            raise ValueError(f"use_cache must be False, True, 'fused' or 'graph', got {use_cache!r}")
+        if sampler not in ("torch", "device"):
+            raise ValueError(f"sampler must be 'torch' or 'device', got {sampler!r}")
+        if sampler == "device" and not fused:
+            raise ValueError("sampler='device' samples inside the fused decode step: use_cache must be 'fused' "
+                             f"or 'graph', got {use_cache!r}")
+        limit = self.context_len
+        B, T = idx.shape
+        if use_cache and max_new_tokens > 0 and T < limit:
+            n = min(max_new_tokens, limit - T + 1)  # the n-th token is drawn from position limit - 1's logits
+            if fused:
+                sess = self.decode_session(B, T + n - 1, graph=use_cache == "graph", sampler=sampler)
+                idx = sess.generate(idx, n, temperature, top_k)
+            else:
+                cache = self.new_cache(B, T + n - 1)
+                logits = self.forward_cached(idx, cache)
+                for step in range(n):
+                    nxt = sample_logits(logits, temperature, top_k)
+                    idx = torch.cat((idx, nxt), dim=1)
+                    if step + 1 < n:
+                        logits = self.forward_cached(nxt, cache)
+            max_new_tokens -= n
+        for _ in range(max_new_tokens):
+            logits, _ = self(idx[:, -limit:])
+            idx = torch.cat((idx, sample_logits(logits[:, -1, :], temperature, top_k)), dim=1)
+        return idx

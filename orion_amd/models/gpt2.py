@@ -24,6 +24,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
+from .generation import Generation
 from .kv_cache import KVCache
 
 
@@ -117,7 +118,7 @@ class Block(nn.Module):
         return x
 
 
-class GPT(nn.Module):
+class GPT(nn.Module, Generation):
     """GPT-2 language model.  ``forward(idx, targets)`` -> (logits|None, loss|None)."""
 
     def __init__(self, cfg: GPTConfig):
@@ -202,18 +203,16 @@ class GPT(nn.Module):
         logits = self.lm_head(x[:, [-1], :])
         return logits, None
 
+    @property
+    def context_len(self):
+        return self.config.block_size
+
     def new_cache(self, batch, max_len=None):
         """An empty :class:`KVCache` for this model on its device (``max_len`` <= block_size)."""
         cfg = self.config
         w = self.lm_head.weight
         return KVCache(cfg.n_layer, batch, min(max_len or cfg.block_size, cfg.block_size), cfg.n_head,
                        cfg.head_dim, device=w.device, dtype=w.dtype)
-
-    def decode_session(self, batch, max_len=None, graph=False, sampler="torch"):
-        """A :class:`DecodeSession` for this model: the fused decode step, captured when ``graph``;
-        ``sampler="device"`` draws the tokens with ``ops.sample_tokens`` inside that step."""
-        from .decode_session import DecodeSession
-        return DecodeSession(self, batch, max_len, graph=graph, sampler=sampler)
 
     @torch.no_grad()
     def forward_cached(self, idx, cache):
@@ -246,58 +245,37 @@ class GPT(nn.Module):
             x, h = ops.add_layer_norm(x, m, nxt.weight, nxt.bias)
         return ops.linear(h[:, -1, :].contiguous(), self.lm_head.weight)
 
-    @staticmethod
-    def _sample(logits, temperature, top_k):
-        logits = logits.float() / max(temperature, 1e-6)
-        if top_k is not None:
-            v, _ = torch.topk(logits, min(top_k, logits.size(-1)))
-            logits[logits < v[:, [-1]]] = -float("inf")
-        return torch.multinomial(F.softmax(logits, dim=-1), num_samples=1)
+    def decode_projections(self):
+        """(name, weight) of every projection of :meth:`decode_step`."""
+        for i, blk in enumerate(self.transformer.h):
+            yield f"h.{i}.attn.c_attn", blk.attn.c_attn.weight
+            yield f"h.{i}.attn.c_proj", blk.attn.c_proj.weight
+            yield f"h.{i}.mlp.c_fc", blk.mlp.c_fc.weight
+            yield f"h.{i}.mlp.c_proj", blk.mlp.c_proj.weight
+        yield "lm_head", self.lm_head.weight
 
-    @torch.no_grad()
-    def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, use_cache=False, sampler="torch"):
-        """nanoGPT's sampling loop.  ``use_cache=True`` keeps every layer's keys / values
-        (:class:`KVCache`): the prompt is prefilled once and each new token costs one single-token
-        forward.  Tokens beyond ``block_size`` take the uncached loop below: cropping the window
-        shifts the learned positions, which invalidates a cache.  ``use_cache="fused"`` runs the
-        cached tokens through a :class:`DecodeSession` (the fused skinny-linear decode step),
-        ``"graph"`` additionally replays that step from one captured HIP graph.  With either,
-        ``sampler="device"`` draws the session's tokens with ``ops.sample_tokens`` inside the step
-        (seeded from torch's default generator) instead of stock torch ops between the steps."""
-        if isinstance(use_cache, str) and use_cache not in ("fused", "graph"):
-            raise ValueError(f"use_cache must be False, True, 'fused' or 'graph', got {use_cache!r}")
-        if sampler not in ("torch", "device"):
-            raise ValueError(f"sampler must be 'torch' or 'device', got {sampler!r}")
-        if sampler == "device" and not isinstance(use_cache, str):
-            raise ValueError("sampler='device' samples inside the fused decode step: use_cache must be 'fused' "
-                             f"or 'graph', got {use_cache!r}")
-        if isinstance(use_cache, str) and max_new_tokens > 0 and idx.size(1) < self.config.block_size:
-            n = min(max_new_tokens, self.config.block_size - idx.size(1) + 1)
-            sess = self.decode_session(idx.size(0), idx.size(1) + n - 1, graph=use_cache == "graph",
-                                       sampler=sampler)
-            idx = sess.generate(idx, n, temperature, top_k)
-            max_new_tokens -= n
-        elif use_cache and max_new_tokens > 0 and idx.size(1) < self.config.block_size:
-            n = min(max_new_tokens, self.config.block_size - idx.size(1) + 1)
-            cache = self.new_cache(idx.size(0), idx.size(1) + n - 1)
-            logits = self.forward_cached(idx, cache)
-            for step in range(n):
-                nxt = self._sample(logits, temperature, top_k)
-                idx = torch.cat((idx, nxt), dim=1)
-                if step + 1 < n:
-                    logits = self.forward_cached(nxt, cache)
-            max_new_tokens -= n
-        for _ in range(max_new_tokens):
-            idx_cond = idx if idx.size(1) <= self.config.block_size else idx[:, -self.config.block_size:]
-            logits, _ = self(idx_cond)
-            logits = logits[:, -1, :].float() / max(temperature, 1e-6)
-            if top_k is not None:
-                v, _ = torch.topk(logits, min(top_k, logits.size(-1)))
-                logits[logits < v[:, [-1]]] = -float("inf")
-            probs = F.softmax(logits, dim=-1)
-            idx_next = torch.multinomial(probs, num_samples=1)
-            idx = torch.cat((idx, idx_next), dim=1)
-        return idx
+    def decode_step(self, tokens, cache, logits_out):
+        """:meth:`forward_cached` at T = 1 for a :class:`DecodeSession`, on device state only:
+        the logits of ``tokens`` (B, 1) at position ``cache.start`` go into ``logits_out``.  Every
+        projection is one ``ops.linear_decode`` with the norm in its prologue and the bias /
+        GELU / residual in its epilogue; the session has advanced ``cache.start`` / ``cache.lens``."""
+        cfg, tr = self.config, self.transformer
+        B, H, D = tokens.shape[0], cfg.n_head, cfg.head_dim
+        x = F.embedding(tokens[:, 0], tr.wte.weight) + F.embedding(cache.start, tr.wpe.weight)
+        for i, blk in enumerate(tr.h):
+            at, ml = blk.attn, blk.mlp
+            qkv = ops.linear_decode(x, at.c_attn.weight, at.c_attn.bias, norm="layer", norm_weight=blk.ln_1.weight,
+                                    norm_bias=blk.ln_1.bias).view(B, 1, 3, H, D)
+            kc, vc = cache.layer(i)
+            ops.kv_append(qkv[:, :, 1], qkv[:, :, 2], kc, vc, cache.start)
+            # the whole cache view: the key split is planned from max_len once and never changes
+            y = ops.attention_decode(qkv[:, 0, 0], kc, vc, cache.lens)
+            x = ops.linear_decode(y.view(B, H * D), at.c_proj.weight, at.c_proj.bias, residual=x)
+            h = ops.linear_decode(x, ml.c_fc.weight, ml.c_fc.bias, norm="layer", norm_weight=blk.ln_2.weight,
+                                  norm_bias=blk.ln_2.bias, act="gelu")
+            x = ops.linear_decode(h, ml.c_proj.weight, ml.c_proj.bias, residual=x)
+        ops.linear_decode(x, self.lm_head.weight, norm="layer", norm_weight=tr.ln_f.weight, norm_bias=tr.ln_f.bias,
+                          out=logits_out)
 
 
 def build_gpt2(preset="gpt2", **overrides):

@@ -37,11 +37,15 @@ class KVCache:
         """(k_cache, v_cache) of layer i, each (B, Tmax, Hkv, D)."""
         return self.buf[i, 0], self.buf[i, 1]
 
+    def check_room(self, T):
+        """Raise ``ValueError``, on the host and before any launch, unless T >= 1 more tokens fit."""
+        if T < 1 or self.pos + T > self.max_len:
+            raise ValueError(f"KVCache overflow: {self.pos} cached + {T} new tokens > max_len {self.max_len}")
+
     def begin(self, T):
         """Reserve T positions for one model forward; returns the position of its first token."""
         T = int(T)
-        if T < 1 or self.pos + T > self.max_len:
-            raise ValueError(f"KVCache overflow: {self.pos} cached + {T} new tokens > max_len {self.max_len}")
+        self.check_room(T)
         pos = self.pos
         self.start.copy_(self.lens)
         self.lens.add_(T)

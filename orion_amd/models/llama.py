@@ -21,9 +21,11 @@ from dataclasses import asdict, dataclass
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from .. import ops
 from ..ops import reference as ref
+from .generation import Generation
 from .kv_cache import KVCache
 
 
@@ -106,7 +108,7 @@ class DecoderLayer(nn.Module):
         self.mlp = FeedForward(cfg)
 
 
-class Llama(nn.Module):
+class Llama(nn.Module, Generation):
     """``forward(idx, targets)`` -> (logits|None, loss|None), same contract as GPT."""
 
     def __init__(self, cfg: LlamaConfig):
@@ -168,18 +170,16 @@ class Llama(nn.Module):
         logits = ops.linear(h[:, [-1], :], self.lm_head.weight)
         return logits, None
 
+    @property
+    def context_len(self):
+        return self.config.max_seq_len
+
     def new_cache(self, batch, max_len=None):
         """An empty :class:`KVCache` for this model on its device (``max_len`` <= max_seq_len)."""
         cfg = self.config
         w = self.lm_head.weight
         return KVCache(cfg.n_layers, batch, min(max_len or cfg.max_seq_len, cfg.max_seq_len), cfg.n_kv_heads,
                        cfg.head_dim, device=w.device, dtype=w.dtype)
-
-    def decode_session(self, batch, max_len=None, graph=False, sampler="torch"):
-        """A :class:`DecodeSession` for this model: the fused decode step, captured when ``graph``;
-        ``sampler="device"`` draws the tokens with ``ops.sample_tokens`` inside that step."""
-        from .decode_session import DecodeSession
-        return DecodeSession(self, batch, max_len, graph=graph, sampler=sampler)
 
     @torch.no_grad()
     def forward_cached(self, idx, cache):
@@ -214,52 +214,39 @@ class Llama(nn.Module):
             x, h = ops.add_rms_norm(x, m, nxt.weight, nxt.eps)
         return ops.linear(h[:, -1, :].contiguous(), self.lm_head.weight)
 
-    @torch.no_grad()
-    def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, use_cache=False, sampler="torch"):
-        """Sampling loop.  ``use_cache=True`` keeps every layer's keys / values
-        (:class:`KVCache`): the prompt is prefilled once and each new token costs one single-token
-        forward; tokens beyond ``max_seq_len`` take the uncached sliding-window loop below.
-        ``use_cache="fused"`` runs the cached tokens through a :class:`DecodeSession` (the fused
-        skinny-linear decode step), ``"graph"`` additionally replays that step from one captured
-        HIP graph.  With either, ``sampler="device"`` draws the session's tokens with
-        ``ops.sample_tokens`` inside the step (seeded from torch's default generator) instead of
-        stock torch ops between the steps."""
-        if isinstance(use_cache, str) and use_cache not in ("fused", "graph"):
-            raise ValueError(f"use_cache must be False, True, 'fused' or 'graph', got {use_cache!r}")
-        if sampler not in ("torch", "device"):
-            raise ValueError(f"sampler must be 'torch' or 'device', got {sampler!r}")
-        if sampler == "device" and not isinstance(use_cache, str):
-            raise ValueError("sampler='device' samples inside the fused decode step: use_cache must be 'fused' "
-                             f"or 'graph', got {use_cache!r}")
-        if isinstance(use_cache, str) and max_new_tokens > 0 and idx.size(1) < self.config.max_seq_len:
-            n = min(max_new_tokens, self.config.max_seq_len - idx.size(1) + 1)
-            sess = self.decode_session(idx.size(0), idx.size(1) + n - 1, graph=use_cache == "graph",
-                                       sampler=sampler)
-            idx = sess.generate(idx, n, temperature, top_k)
-            max_new_tokens -= n
-        elif use_cache and max_new_tokens > 0 and idx.size(1) < self.config.max_seq_len:
-            n = min(max_new_tokens, self.config.max_seq_len - idx.size(1) + 1)
-            cache = self.new_cache(idx.size(0), idx.size(1) + n - 1)
-            logits = self.forward_cached(idx, cache)
-            for step in range(n):
-                logits = logits.float() / max(temperature, 1e-6)
-                if top_k is not None:
-                    v, _ = torch.topk(logits, min(top_k, logits.size(-1)))
-                    logits[logits < v[:, [-1]]] = -float("inf")
-                nxt = torch.multinomial(torch.softmax(logits, -1), 1)
-                idx = torch.cat((idx, nxt), dim=1)
-                if step + 1 < n:
-                    logits = self.forward_cached(nxt, cache)
-            max_new_tokens -= n
-        for _ in range(max_new_tokens):
-            cond = idx[:, -self.config.max_seq_len:]
-            logits, _ = self(cond)
-            logits = logits[:, -1, :].float() / max(temperature, 1e-6)
-            if top_k is not None:
-                v, _ = torch.topk(logits, min(top_k, logits.size(-1)))
-                logits[logits < v[:, [-1]]] = -float("inf")
-            idx = torch.cat((idx, torch.multinomial(torch.softmax(logits, -1), 1)), dim=1)
-        return idx
+    def decode_projections(self):
+        """(name, weight) of every projection of :meth:`decode_step`."""
+        for i, layer in enumerate(self.layers):
+            yield f"layers.{i}.self_attn.qkv_proj", layer.self_attn.qkv_proj.weight
+            yield f"layers.{i}.self_attn.o_proj", layer.self_attn.o_proj.weight
+            yield f"layers.{i}.mlp.gate_up_proj", layer.mlp.gate_up_proj.weight
+            yield f"layers.{i}.mlp.down_proj", layer.mlp.down_proj.weight
+        yield "lm_head", self.lm_head.weight
+
+    def decode_step(self, tokens, cache, logits_out):
+        """:meth:`forward_cached` at T = 1 for a :class:`DecodeSession`, on device state only:
+        the logits of ``tokens`` (B, 1) at position ``cache.start`` go into ``logits_out``.  Every
+        projection is one ``ops.linear_decode`` with the norm in its prologue and the SwiGLU /
+        residual in its epilogue; the session has advanced ``cache.start`` / ``cache.lens``."""
+        cfg = self.config
+        B, Hq, Hkv, D = tokens.shape[0], cfg.n_heads, cfg.n_kv_heads, cfg.head_dim
+        cos, sin = self.rope_cos, self.rope_sin
+        x = F.embedding(tokens[:, 0], self.embed_tokens.weight)
+        for i, layer in enumerate(self.layers):
+            at, ff = layer.self_attn, layer.mlp
+            ln1, ln2 = layer.input_layernorm, layer.post_attention_layernorm
+            qkv = ops.linear_decode(x, at.qkv_proj.weight, norm="rms", norm_weight=ln1.weight,
+                                    eps=ln1.eps).view(B, 1, Hq + 2 * Hkv, D)
+            kc, vc = cache.layer(i)
+            q = ops.kv_append(qkv[:, :, Hq:Hq + Hkv], qkv[:, :, Hq + Hkv:], kc, vc, cache.start,
+                              q=qkv[:, :, :Hq], cos=cos, sin=sin)
+            y = ops.attention_decode(q[:, 0], kc, vc, cache.lens)
+            x = ops.linear_decode(y.view(B, Hq * D), at.o_proj.weight, residual=x)
+            h = ops.linear_decode(x, ff.gate_up_proj.weight, norm="rms", norm_weight=ln2.weight, eps=ln2.eps,
+                                  act="swiglu")
+            x = ops.linear_decode(h, ff.down_proj.weight, residual=x)
+        ops.linear_decode(x, self.lm_head.weight, norm="rms", norm_weight=self.norm.weight, eps=self.norm.eps,
+                          out=logits_out)
 
 
 def build_llama(preset="llama2-7b", **overrides):

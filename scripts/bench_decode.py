@@ -149,7 +149,7 @@ def bench_linear(model, name, N, K, norm, act, bias, residual, M, rounds):
 def bench_sample(B, V, top_k, rounds):
     """Device time of one ``ops.sample_tokens`` launch beside ``sample_logits`` on the same logits
     (rotating over 8 logits buffers; both draw their own random numbers)."""
-    from orion_amd.models.decode_session import sample_logits
+    from orion_amd.models.generation import sample_logits
     from orion_amd.ops.decode import sample_params
     g = torch.Generator(device="cuda").manual_seed(0)
     logits = [(torch.randn(B, V, device="cuda", generator=g) * 2.5).to(torch.bfloat16) for _ in range(8)]
@@ -176,7 +176,7 @@ def bench_sample(B, V, top_k, rounds):
 def bench_graph_steady(model, B, prompt_len, new_tokens):
     """The graph arm without its capture: per-token time of the sampling loop on a captured
     session, and of the replay alone (the rest is the sampling launches)."""
-    from orion_amd.models.decode_session import sample_logits
+    from orion_amd.models.generation import sample_logits
     prompt = torch.randint(0, 50257, (B, prompt_len), device="cuda")
     sess = model.decode_session(B, prompt_len + new_tokens, graph=True)
     logits = sess.prefill(prompt)

@@ -211,6 +211,97 @@ def test_generate_true_and_false_keep_their_random_stream(name):
     assert torch.equal(got_plain, idx)
 
 
+def _draw(logits, temp, top_k):
+    """The sampling rule, written out here: the tests below pin ``generate`` against it."""
+    logits = logits.float() / temp
+    v, _ = torch.topk(logits, top_k)
+    logits[logits < v[:, [-1]]] = -float("inf")
+    return torch.multinomial(torch.softmax(logits, -1), 1)
+
+
+def _hand_rolled(model, prompt, new, mode, temp, top_k, limit=None):
+    """``new`` tokens after ``prompt``: the first n from ``forward_cached`` (mode True) or a
+    :class:`DecodeSession` (``"fused"`` / ``"graph"``), the rest from the plain forward on the
+    last ``limit`` tokens.  Without a limit every token is a cached one."""
+    T = prompt.size(1)
+    n = new if limit is None else min(new, limit - T + 1) if T < limit else 0
+    idx = prompt
+    with torch.no_grad():
+        if n > 0:
+            if mode is True:
+                cache = model.new_cache(B, T + n - 1)
+                first, step = model.forward_cached(prompt, cache), lambda tok: model.forward_cached(tok, cache)
+            else:
+                sess = model.decode_session(B, T + n - 1, graph=mode == "graph")
+                first, step = sess.prefill(prompt), sess.step
+            logits = first
+            for i in range(n):
+                nxt = _draw(logits, temp, top_k)
+                idx = torch.cat((idx, nxt), 1)
+                if i + 1 < n:
+                    logits = step(nxt)
+        for _ in range(new - n):
+            idx = torch.cat((idx, _draw(model(idx[:, -limit:])[0][:, -1, :], temp, top_k)), 1)
+    return idx
+
+
+@pytest.mark.parametrize("mode", ["fused", "graph"])
+@pytest.mark.parametrize("name", ["gpt2-tiny", "llama-tiny"])
+def test_generate_fused_and_graph_keep_their_random_stream(name, mode):
+    """As the test above for use_cache="fused" / "graph" with the default sampler: a hand-rolled
+    loop over ``decode_session(...).prefill`` / ``.step`` under the same seed, token for token."""
+    model = _model(name)
+    g = torch.Generator().manual_seed(4)
+    prompt = torch.randint(0, model.config.vocab_size, (B, 5), generator=g)
+    torch.manual_seed(7)
+    got = model.generate(prompt, 6, temperature=0.8, top_k=10, use_cache=mode)
+    torch.manual_seed(7)
+    assert torch.equal(got, _hand_rolled(model, prompt, 6, mode, 0.8, 10))
+
+
+@pytest.mark.parametrize("plen,new", [(30, 8), (32, 3), (31, 1)],
+                         ids=["3-cached-5-window", "window-only", "1-cached"])
+@pytest.mark.parametrize("mode", [True, "fused", "graph"])
+@pytest.mark.parametrize("name", ["gpt2-tiny", "llama-tiny"])
+def test_generate_hands_over_at_the_context_limit(name, mode, plen, new):
+    """Context limit 32: ``n = min(new, 32 - T + 1)`` tokens come from the cache or the session (a
+    prompt that fills the window has none), the rest from ``model(idx[:, -32:])``; exact under
+    the same seed."""
+    model = _model(name, **({"block_size": 32} if name == "gpt2-tiny" else {"max_seq_len": 32}))
+    g = torch.Generator().manual_seed(3)
+    prompt = torch.randint(0, model.config.vocab_size, (B, plen), generator=g)
+    torch.manual_seed(7)
+    got = model.generate(prompt, new, temperature=0.8, top_k=10, use_cache=mode)
+    torch.manual_seed(7)
+    want = _hand_rolled(model, prompt, new, mode, 0.8, 10, limit=32)
+    assert got.shape == (B, plen + new) and torch.equal(got, want)
+
+
+@pytest.mark.parametrize("name", ["gpt2-tiny", "llama-tiny"])
+def test_every_torch_sampler_mode_draws_through_sample_logits(name, monkeypatch):
+    """One rule: ``generate`` of the model in its four torch-sampler modes and
+    ``DecodeSession.generate`` call ``generation.sample_logits`` once per new token."""
+    from orion_amd.models import generation
+    calls = []
+    rule = generation.sample_logits
+
+    def counting(logits, temperature=1.0, top_k=None):
+        calls.append((tuple(logits.shape), temperature, top_k))
+        return rule(logits, temperature, top_k)
+
+    monkeypatch.setattr(generation, "sample_logits", counting)
+    model = _model(name)
+    prompt = torch.zeros(B, 5, dtype=torch.long)
+    V = model.config.vocab_size
+    for mode in (False, True, "fused", "graph"):
+        del calls[:]
+        model.generate(prompt, 6, temperature=0.8, top_k=10, use_cache=mode)
+        assert calls == [((B, V), 0.8, 10)] * 6, mode
+    del calls[:]
+    model.decode_session(B, 16).generate(prompt, 4, 0.7, 3)
+    assert calls == [((B, V), 0.7, 3)] * 4
+
+
 @pytest.mark.parametrize("graph", [False, True])
 def test_step_raises_before_overflow(graph):
     model = _model("gpt2-tiny")
