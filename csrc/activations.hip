@@ -6,6 +6,7 @@
 // registers (no second pass over the (rows, 4C) activation).
 #include <cstdlib>
 #include "common.h"
+#include "launchers.h"
 
 namespace orion {
 
@@ -195,8 +196,6 @@ static inline int ew_grid(long n8) {
   long g = (n8 + 255) / 256;
   return (int)(g < cap ? (g < 1 ? 1 : g) : cap);
 }
-
-int orion_layernorm_bwd_blocks(int rows);
 
 int orion_bias_gelu_fwd(const void* x, const void* b, void* y, long n, int C, hipStream_t st) {
   if (C % 8 || n % 8) return -1;

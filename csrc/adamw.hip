@@ -8,6 +8,7 @@
 // 26 bytes/element of HBM traffic: the 124M-parameter step is ~3.2 GB, ~0.6 ms.
 #include <cstdlib>
 #include "common.h"
+#include "launchers.h"
 
 // non-temporal loads / stores for the once-per-step streams (A/B builds: -DADAMW_NT=0/1)
 #ifndef ADAMW_NT

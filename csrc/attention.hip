@@ -43,7 +43,7 @@
 #include <type_traits>
 
 #include "common.h"
-#include "attn_params.h"
+#include "launchers.h"
 #include "mfma_lds.h"
 
 namespace orion {
@@ -559,8 +559,6 @@ static void set_lds_attr() {
     done = true;
   }
 }
-
-int orion_attn_fwd3(const AttnParams& p, int D, bool causal, hipStream_t st);  // attn_fwd.hip
 
 // ORION_ATTN_FWD=v2 selects the kernel below (A/B measurement); default: attn_fwd.hip
 static bool fwd_v2() {

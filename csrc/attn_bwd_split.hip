@@ -31,7 +31,7 @@
 #include <type_traits>
 
 #include "common.h"
-#include "attn_params.h"
+#include "launchers.h"
 #include "mfma_lds.h"
 
 namespace orion {

@@ -26,8 +26,8 @@
 // of q | k_new | v_new; k (rotated in fp32 at position kv_lens[b] + t when tables are given,
 // rounded once) and v (copied bit for bit) land in the cache, the rotated q in a contiguous
 // output.  Positions outside [0, Tmax) are skipped (their q rows are zero).
-#include "attn_decode_params.h"
 #include "common.h"
+#include "launchers.h"
 
 namespace orion {
 
@@ -330,7 +330,7 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const AppendParams p) {
 
 using namespace orion;
 
-int orion_attn_decode_tile(int D) { return D == 64 ? DecodeShape<64>::TILE : DecodeShape<128>::TILE; }
+static int orion_attn_decode_tile(int D) { return D == 64 ? DecodeShape<64>::TILE : DecodeShape<128>::TILE; }
 
 // Splits chosen on the host from the caller's upper bound on the length (the cache view's
 // Tmax): enough workgroups for two per CU of the 256 when the length allows, each split a

@@ -26,7 +26,7 @@
 #include <type_traits>
 
 #include "common.h"
-#include "attn_params.h"
+#include "launchers.h"
 #include "mfma_lds.h"
 
 #ifndef ATTN_FWD_QB64

@@ -14,72 +14,7 @@
 #include <cstring>
 #include <tuple>
 
-#include "attn_decode_params.h"
-#include "attn_params.h"
-#include "linear_decode_params.h"
-#include "sample_params.h"
-
-// launchers (csrc/*.hip)
-int orion_layernorm_fwd(const void*, const void*, const void*, void*, float*, float*, int, int,
-                        float, const void*, void*, const void*, hipStream_t,
-                        const int64_t* idx = nullptr, int T = 0, long V = 0, int* err = nullptr);
-int orion_embed_scatter_add(const void*, const int64_t*, float*, long, int, long, int*, hipStream_t);
-int orion_batch_sum(const void*, void*, int, long, int, hipStream_t);
-int orion_layernorm_bwd_blocks(int rows);
-int orion_layernorm_bwd(const void*, const void*, const void*, const float*, const float*, void*,
-                        void*, void*, float*, int, int, const void*, void*, int, hipStream_t);
-int orion_colsum_bf16(const void*, void*, float*, int, int, int, hipStream_t);
-int orion_bias_gelu_fwd(const void*, const void*, void*, long, int, hipStream_t);
-int orion_bias_gelu_bwd(const void*, const void*, const void*, void*, float*, int, int, hipStream_t);
-int orion_colsum_partials2(const float*, float*, void*, int, int, int, hipStream_t);
-int orion_colsum_scratch(int rows, int C);
-int orion_swiglu_fwd(const void*, void*, long, int, hipStream_t);
-int orion_swiglu_bwd(const void*, const void*, void*, long, int, hipStream_t);
-int orion_scale_bf16(void*, const float*, long, hipStream_t);
-int orion_slab_sum(const float*, int, long, void*, const float*, int, int, hipStream_t);
-int orion_wgrad_splits(int, int, int);
-int orion_wgrad_effective_splits(int, int);
-int orion_wgrad_tail_rows(int, int, int, int*);
-int orion_wgrad(const void*, long, const void*, long, int, int, int, int, float*, void*,
-                const float*, int, int, int, hipStream_t);
-int orion_xent_fwd_bwd(void*, const int64_t*, float*, float*, float*, long, int, long, int*, hipStream_t);
-int orion_sumsq_partials();
-int orion_grad_sumsq(const void*, long, int, float*, float*, hipStream_t);
-int orion_adamw_flat(void*, float*, float*, float*, const void*, int, const uint8_t*, const float*,
-                     const float*, long, hipStream_t);
-int orion_rmsnorm_fwd(const void*, const void*, void*, float*, int, int, float, const void*, void*,
-                      hipStream_t);
-int orion_rmsnorm_bwd_blocks(int rows);
-int orion_rmsnorm_bwd(const void*, const void*, const void*, const float*, void*, void*, float*,
-                      int, int, const void*, int, hipStream_t);
-int orion_rope(const void*, long, long, long, void*, long, long, long, const float*, const float*,
-               int, int, int, int, int, float, hipStream_t);
-int orion_attn_fwd(const orion::AttnParams&, int, bool, hipStream_t);
-int orion_attn_bwd(const orion::AttnParams&, int, bool, float*, hipStream_t);
-int orion_attn_dq_convert(const float*, void*, long, long, long, int, int, int, int, hipStream_t);
-int orion_attn_bwd_split(const orion::AttnParams&, int, bool, float*, hipStream_t);
-int orion_gemm(const void*, long, const void*, long, int, int, int, int, int, void*, long,
-               const void*, void*, long, const void*, long, hipStream_t, void* db = nullptr,
-               int db_f32 = 0, float* part = nullptr);
-int orion_gemm_colsum_scratch(int M, int N);
-int orion_gemm_lm(const void*, long, const void*, long, int, int, int, int, void*, long, float*,
-                  const int64_t*, float*, const float*, const float*, hipStream_t);
-int orion_gemm_rope(const void*, long, const void*, long, int, int, int, void*, long, const float*, const float*,
-                    int, int, int, int, hipStream_t);
-int orion_gemm_swiglu(const void*, long, const void*, long, int, int, int, void*, long, void*, long, hipStream_t);
-int orion_blaslt_linear_res(const void*, long, const void*, long, const void*, const void*, long, void*, long, int,
-                            int, int, hipStream_t);
-int orion_lmhead_fold(const float*, int, const float*, const int64_t*, long, float*, void*, long, int, long,
-                      const void*, long, const void*, long, int, float*, float*, float*, int*, int*, float*,
-                      float*, int*, hipStream_t);
-int orion_lmhead_bwd_prep(const void*, long, int, long, const int64_t*, long, int, const float*, const float*,
-                          const float*, float*, void*, int, hipStream_t);
-int orion_gemm_set_diag(int flags);
-int orion_attn_decode_plan(int, int, int, int, int, int*);
-int orion_attn_decode(const orion::DecodeParams&, int, hipStream_t);
-int orion_kv_append(const orion::AppendParams&, hipStream_t);
-int orion_linear_decode(const orion::LinearDecodeParams&, hipStream_t);
-int orion_sample_tokens(const orion::SampleParams&, hipStream_t);
+#include "launchers.h"
 
 namespace {
 
@@ -121,14 +56,45 @@ void check_grad_out(const Tensor& t, const char* name) {
 
 int is_f32(const Tensor& t) { return t.scalar_type() == at::kFloat ? 1 : 0; }
 
+constexpr double LOG2E = 1.4426950408889634;
+bool given(const c10::optional<Tensor>& o) { return o.has_value() && o->defined(); }
+
 // an optional in-place output (a parameter's gradient-arena slice, ops/grad_sink.py): must be
 // a contiguous bf16 or fp32 vector of n elements
 bool has_out(const c10::optional<Tensor>& o, int64_t n, const char* name) {
-  if (!o.has_value() || !o->defined()) return false;
+  if (!given(o)) return false;
   check_grad_out(*o, name);
   TORCH_CHECK(o->is_contiguous() && o->numel() == n, name, " must be contiguous with ", n,
               " elements, got ", o->sizes());
   return true;
+}
+
+// an optional bf16 operand, checked and made contiguous (`keep` holds the copy): its pointer or null
+const void* opt_bf16(const c10::optional<Tensor>& o, const char* name, Tensor& keep) {
+  if (!given(o)) return nullptr;
+  check_bf16(*o, name);
+  keep = o->contiguous();
+  return keep.data_ptr();
+}
+
+// an optional one-element fp32 device scalar (slab_sum, wgrad_into)
+const float* opt_scale(const c10::optional<Tensor>& scale) {
+  if (!given(scale)) return nullptr;
+  TORCH_CHECK(scale->scalar_type() == at::kFloat && scale->numel() == 1, "scale must be one fp32");
+  return scale->data_ptr<float>();
+}
+
+// x (..., C) as a matrix: {rows, C}
+std::pair<int, int> rows_cols(const Tensor& x) {
+  const int C = x.size(-1);
+  return {(int)(x.numel() / C), C};
+}
+
+// a (B, T, H, D) bf16 view into a params struct: base pointer and the three outer strides
+template <class P>
+void set_view(P*& ptr, long& sb, long& st, long& sh, const Tensor& t) {
+  ptr = (P*)t.data_ptr();
+  sb = t.stride(0); st = t.stride(1); sh = t.stride(2);
 }
 
 // ------------------------------------------------------------------ layernorm
@@ -138,18 +104,12 @@ std::tuple<Tensor, Tensor, Tensor> layernorm_fwd(const Tensor& x, const Tensor& 
   check_bf16(w, "weight");
   c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
   auto xc = x.contiguous();
-  const int C = x.size(-1);
-  const int rows = x.numel() / C;
+  const auto [rows, C] = rows_cols(x);
   auto y = at::empty_like(xc);
   auto opts = x.options().dtype(at::kFloat);
   auto mean = at::empty({rows}, opts), rstd = at::empty({rows}, opts);
-  const void* bp = nullptr;
   Tensor bc;
-  if (b.has_value() && b->defined()) {
-    check_bf16(*b, "bias");
-    bc = b->contiguous();
-    bp = bc.data_ptr();
-  }
+  const void* bp = opt_bf16(b, "bias", bc);
   check_launch(orion_layernorm_fwd(xc.data_ptr(), w.contiguous().data_ptr(), bp, y.data_ptr(),
                                    mean.data_ptr<float>(), rstd.data_ptr<float>(), rows, C,
                                    (float)eps, nullptr, nullptr, nullptr, cur_stream()),
@@ -169,26 +129,16 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> add_layernorm_fwd(const Tensor& x, co
   TORCH_CHECK(x.sizes() == r.sizes(), "add_layernorm: shape mismatch");
   c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
   auto xc = x.contiguous(), rc = r.contiguous();
-  const int C = x.size(-1);
-  const int rows = x.numel() / C;
+  const auto [rows, C] = rows_cols(x);
   auto y = at::empty_like(xc), sum = at::empty_like(xc);
   auto opts = x.options().dtype(at::kFloat);
   auto mean = at::empty({rows}, opts), rstd = at::empty({rows}, opts);
-  const void* bp = nullptr;
   Tensor bc, rbc;
-  if (b.has_value() && b->defined()) {
-    check_bf16(*b, "bias");
-    bc = b->contiguous();
-    bp = bc.data_ptr();
-  }
-  if (rbias.has_value() && rbias->defined()) {
-    check_bf16(*rbias, "branch bias");
-    rbc = rbias->contiguous();
-  }
+  const void* bp = opt_bf16(b, "bias", bc);
+  const void* rbp = opt_bf16(rbias, "branch bias", rbc);
   check_launch(orion_layernorm_fwd(xc.data_ptr(), w.contiguous().data_ptr(), bp, y.data_ptr(),
                                    mean.data_ptr<float>(), rstd.data_ptr<float>(), rows, C,
-                                   (float)eps, rc.data_ptr(), sum.data_ptr(),
-                                   rbc.defined() ? rbc.data_ptr() : nullptr, cur_stream()),
+                                   (float)eps, rc.data_ptr(), sum.data_ptr(), rbp, cur_stream()),
                "add_layernorm_fwd");
   return {sum, y, mean, rstd};
 }
@@ -215,13 +165,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> embed_layernorm_fwd(const Tensor& idx
   auto y = at::empty({idx.size(0), T, C}, opts), sum = at::empty({idx.size(0), T, C}, opts);
   auto fopts = opts.dtype(at::kFloat);
   auto mean = at::empty({rows}, fopts), rstd = at::empty({rows}, fopts);
-  const void* bp = nullptr;
   Tensor bc;
-  if (b.has_value() && b->defined()) {
-    check_bf16(*b, "bias");
-    bc = b->contiguous();
-    bp = bc.data_ptr();
-  }
+  const void* bp = opt_bf16(b, "bias", bc);
   auto wtec = wte.contiguous(), wpec = wpe.contiguous();
   check_launch(orion_layernorm_fwd(wtec.data_ptr(), w.contiguous().data_ptr(), bp, y.data_ptr(),
                                    mean.data_ptr<float>(), rstd.data_ptr<float>(), rows, C,
@@ -284,8 +229,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> layernorm_bwd(const Tensor& dy, const
                                                          const c10::optional<Tensor>& dxs_out) {
   c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
   auto dyc = dy.contiguous(), xc = x.contiguous();
-  const int C = x.size(-1);
-  const int rows = x.numel() / C;
+  const auto [rows, C] = rows_cols(x);
   auto dx = at::empty_like(xc);
   // a given *_out (a parameter's gradient-arena slice, ops/grad_sink.py) is written in place
   // and its return slot is left undefined
@@ -295,25 +239,20 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> layernorm_bwd(const Tensor& dy, const
   // converts returned gradients to the parameter dtype)
   int f32 = 0;
   for (auto* o : {&dw_out, &db_out, &dxs_out})
-    if (o->has_value() && (*o)->defined()) f32 |= is_f32(**o);
+    if (given(*o)) f32 |= is_f32(**o);
   for (auto* o : {&dw_out, &db_out, &dxs_out})
-    if (o->has_value() && (*o)->defined())
-      TORCH_CHECK(is_f32(**o) == f32, "layernorm_bwd: gradient outputs must share one dtype");
+    if (given(*o)) TORCH_CHECK(is_f32(**o) == f32, "layernorm_bwd: gradient outputs must share one dtype");
   auto gopts = f32 ? w.options().dtype(at::kFloat) : w.options();
   Tensor dw = w_in ? *dw_out : at::empty({C}, gopts);
   Tensor db = has_bias ? (b_in ? *db_out : at::empty({C}, gopts)) : Tensor();
-  const int nb = orion_layernorm_bwd_blocks(rows);
-  auto part = at::empty({3 * (long)nb * C + 48L * C}, x.options().dtype(at::kFloat));
+  auto part = at::empty({orion_layernorm_bwd_scratch(rows, C)}, x.options().dtype(at::kFloat));
   Tensor dxs = want_dx_colsum ? (s_in ? *dxs_out : at::empty({C}, f32 ? gopts : x.options())) : Tensor();
   Tensor drc;
-  if (dres.has_value() && dres->defined()) {
-    check_bf16(*dres, "dres");
-    drc = dres->contiguous();
-  }
+  const void* drp = opt_bf16(dres, "dres", drc);
   check_launch(orion_layernorm_bwd(dyc.data_ptr(), xc.data_ptr(), w.contiguous().data_ptr(),
                                    mean.data_ptr<float>(), rstd.data_ptr<float>(), dx.data_ptr(),
                                    dw.data_ptr(), has_bias ? db.data_ptr() : nullptr,
-                                   part.data_ptr<float>(), rows, C, drc.defined() ? drc.data_ptr() : nullptr,
+                                   part.data_ptr<float>(), rows, C, drp,
                                    want_dx_colsum ? dxs.data_ptr() : nullptr, f32, cur_stream()),
                "layernorm_bwd");
   return {dx, w_in ? Tensor() : dw, b_in ? Tensor() : db, s_in ? Tensor() : dxs};
@@ -327,12 +266,7 @@ Tensor bias_gelu_fwd(const Tensor& x, const c10::optional<Tensor>& b) {
   auto y = at::empty_like(xc);
   const int C = x.size(-1);
   Tensor bc;
-  const void* bp = nullptr;
-  if (b.has_value() && b->defined()) {
-    check_bf16(*b, "bias");
-    bc = b->contiguous();
-    bp = bc.data_ptr();
-  }
+  const void* bp = opt_bf16(b, "bias", bc);
   check_launch(orion_bias_gelu_fwd(xc.data_ptr(), bp, y.data_ptr(), xc.numel(), C, cur_stream()),
                "bias_gelu_fwd");
   return y;
@@ -343,17 +277,17 @@ std::tuple<Tensor, Tensor> bias_gelu_bwd(const Tensor& dy, const Tensor& x,
                                          const c10::optional<Tensor>& db_out) {
   c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
   auto dyc = dy.contiguous(), xc = x.contiguous();
-  const int C = x.size(-1);
-  const int rows = x.numel() / C;
+  const auto [rows, C] = rows_cols(x);
   auto dx = at::empty_like(xc);
-  Tensor db, bc;
+  Tensor db, bc, partt;
   const void* bp = nullptr;
   float* part = nullptr;
-  Tensor partt;
-  if (b.has_value() && b->defined()) {
+  bool db_in = false;  // db_out is looked at (and checked) only with a bias
+  if (given(b)) {
     bc = b->contiguous();
     bp = bc.data_ptr();
-    db = has_out(db_out, C, "db_out") ? *db_out : at::empty({C}, b->options());
+    db_in = has_out(db_out, C, "db_out");
+    db = db_in ? *db_out : at::empty({C}, b->options());
     partt = at::empty({(long)orion_colsum_scratch(rows, C)}, x.options().dtype(at::kFloat));
     part = partt.data_ptr<float>();
   }
@@ -366,17 +300,16 @@ std::tuple<Tensor, Tensor> bias_gelu_bwd(const Tensor& dy, const Tensor& x,
                                         is_f32(db), cur_stream()),
                  "colsum");
   }
-  return {dx, (db.defined() && has_out(db_out, C, "db_out")) ? Tensor() : db};
+  return {dx, db_in ? Tensor() : db};
 }
 
 Tensor colsum(const Tensor& m, const c10::optional<Tensor>& out_) {
   check_bf16(m, "m");
   c10::hip::HIPGuardMasqueradingAsCUDA g(m.device());
   auto mc = m.contiguous();
-  const int C = m.size(-1);
-  const int rows = m.numel() / C;
-  const bool given = has_out(out_, C, "out");
-  auto out = given ? *out_ : at::empty({C}, m.options());
+  const auto [rows, C] = rows_cols(m);
+  const bool out_in = has_out(out_, C, "out");
+  auto out = out_in ? *out_ : at::empty({C}, m.options());
   auto part = at::empty({(long)orion_colsum_scratch(rows, C)}, m.options().dtype(at::kFloat));
   check_launch(orion_colsum_bf16(mc.data_ptr(), out.data_ptr(), part.data_ptr<float>(), rows, C,
                                  is_f32(out), cur_stream()),
@@ -516,7 +449,7 @@ Tensor linear_residual(const Tensor& x, const Tensor& w, const c10::optional<Ten
                        const c10::optional<Tensor>& r_in) {
   check_bf16(x, "x");
   check_bf16(w, "w");
-  const bool hb = bias_in.has_value() && bias_in->defined(), hr = r_in.has_value() && r_in->defined();
+  const bool hb = given(bias_in), hr = given(r_in);
   if (hb) check_bf16(*bias_in, "bias");
   if (hr) check_bf16(*r_in, "r");
   TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.stride(1) == 1 && w.is_contiguous() && x.size(1) == w.size(1) &&
@@ -595,11 +528,7 @@ Tensor slab_sum(const Tensor& slabs, const c10::optional<Tensor>& scale) {
   c10::hip::HIPGuardMasqueradingAsCUDA g(slabs.device());
   const int S = slabs.size(0);
   auto out = at::empty(slabs.sizes().slice(1), slabs.options().dtype(at::kBFloat16));
-  const float* sc = nullptr;
-  if (scale.has_value() && scale->defined()) {
-    TORCH_CHECK(scale->scalar_type() == at::kFloat && scale->numel() == 1, "scale must be one fp32");
-    sc = scale->data_ptr<float>();
-  }
+  const float* sc = opt_scale(scale);
   check_launch(orion_slab_sum(slabs.data_ptr<float>(), S, out.numel(), out.data_ptr(), sc, 0, 0,
                               cur_stream()),
                "slab_sum");
@@ -624,11 +553,7 @@ void wgrad_into(const Tensor& dy, const Tensor& x_in, const c10::optional<Tensor
   TORCH_CHECK(out.is_contiguous() && out.numel() == (int64_t)N1 * N2, "wgrad: out must be contiguous (N1, N2)");
   c10::hip::HIPGuardMasqueradingAsCUDA g(dy.device());
   int S = splits > 0 ? orion_wgrad_effective_splits(M, (int)splits) : orion_wgrad_splits(M, N1, N2);
-  const float* sc = nullptr;
-  if (scale.has_value() && scale->defined()) {
-    TORCH_CHECK(scale->scalar_type() == at::kFloat && scale->numel() == 1, "scale must be one fp32");
-    sc = scale->data_ptr<float>();
-  }
+  const float* sc = opt_scale(scale);
   int S2 = 1;
   const int R1 = splits > 0 ? 0 : orion_wgrad_tail_rows(M, N1, N2, &S2);
   if (R1 > 0) {  // whole rounds unsplit, the tail rows split-K (orion_wgrad_tail_rows)
@@ -703,17 +628,15 @@ std::tuple<Tensor, Tensor> gemm(const Tensor& x, const Tensor& w, bool w_kmajor,
   const void* pp = nullptr;
   long ldp = 0;
   if (epi == 1 || epi == 2) {
-    TORCH_CHECK(bias.has_value() && bias->defined(), "gemm: epilogue needs a bias");
-    check_bf16(*bias, "bias");
-    bc = bias->contiguous();
+    TORCH_CHECK(given(bias), "gemm: epilogue needs a bias");
+    bp = opt_bf16(bias, "bias", bc);
     TORCH_CHECK(bc.numel() == N, "gemm: bias must have N elements");
-    bp = bc.data_ptr();
   }
   if (epi == 2) out2 = at::empty(sizes, x.options());
-  if (epi <= 2 && pre.has_value() && pre->defined() && pre->nbytes() >= 8 * 8 * 1024)
+  if (epi <= 2 && given(pre) && pre->nbytes() >= 8 * 8 * 1024)
     pp = pre->data_ptr();  // diagnostic: the gemm_diag(4) slot-stamp buffer (scripts/gemm16_stamps.py)
   if (epi == 3) {
-    TORCH_CHECK(pre.has_value() && pre->defined(), "gemm: GELU backward needs the pre-activation");
+    TORCH_CHECK(given(pre), "gemm: GELU backward needs the pre-activation");
     check_bf16(*pre, "pre");
     pc = pre->reshape({-1, N});
     TORCH_CHECK(pc.size(0) == M && pc.stride(1) == 1, "gemm: pre must be (M, N) with unit column stride");
@@ -748,24 +671,19 @@ std::tuple<Tensor, Tensor> gemm_gelu_bwd(const Tensor& dy, const Tensor& w, cons
   TORCH_CHECK(pc.size(0) == M && pc.stride(1) == 1, "gemm_gelu_bwd: pre must be (M, N)");
   c10::hip::HIPGuardMasqueradingAsCUDA g(dy.device());
   Tensor bc;
-  const void* bp = nullptr;
-  if (bias.has_value() && bias->defined()) {
-    check_bf16(*bias, "bias");
-    bc = bias->contiguous();
-    TORCH_CHECK(bc.numel() == N, "gemm_gelu_bwd: bias must have N elements");
-    bp = bc.data_ptr();
-  }
+  const void* bp = opt_bf16(bias, "bias", bc);
+  if (given(bias)) TORCH_CHECK(bc.numel() == N, "gemm_gelu_bwd: bias must have N elements");
   auto sizes = pre.sizes().vec();
   auto out = at::empty({M, N}, dy.options());
-  const bool given = has_out(db_out, N, "db_out");
-  auto db = given ? *db_out : at::empty({N}, bias.has_value() && bias->defined() ? bias->options() : dy.options());
+  const bool db_in = has_out(db_out, N, "db_out");
+  auto db = db_in ? *db_out : at::empty({N}, given(bias) ? bias->options() : dy.options());
   auto part = at::empty({(long)orion_gemm_colsum_scratch((int)M, (int)N)}, dy.options().dtype(at::kFloat));
   check_launch(orion_gemm(x2.data_ptr(), x2.stride(0), w.data_ptr(), w.stride(0), (int)M, (int)N,
                           (int)K, 1, 3 | (pre_is_deriv ? 0x100 : 0), out.data_ptr(), N, bp, nullptr, 0,
                           pc.data_ptr(), pc.stride(0), cur_stream(), db.data_ptr(), is_f32(db) ? 1 : 0,
                           part.data_ptr<float>()),
                "gemm_gelu_bwd");
-  return {out.view(sizes), given ? Tensor() : db};
+  return {out.view(sizes), db_in ? Tensor() : db};
 }
 
 // dgate_up = SwiGLU'(gate_up) applied to dy . w: the fused backward of silu(gate) * up ->
@@ -829,8 +747,7 @@ std::tuple<Tensor, Tensor> rmsnorm_fwd(const Tensor& x, const Tensor& w, double 
   check_bf16(w, "weight");
   c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
   auto xc = x.contiguous();
-  const int C = x.size(-1);
-  const int rows = x.numel() / C;
+  const auto [rows, C] = rows_cols(x);
   auto y = at::empty_like(xc);
   auto rstd = at::empty({rows}, x.options().dtype(at::kFloat));
   check_launch(orion_rmsnorm_fwd(xc.data_ptr(), w.contiguous().data_ptr(), y.data_ptr(),
@@ -849,8 +766,7 @@ std::tuple<Tensor, Tensor, Tensor> add_rmsnorm_fwd(const Tensor& x, const Tensor
   TORCH_CHECK(x.sizes() == r.sizes(), "add_rmsnorm: shape mismatch");
   c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
   auto xc = x.contiguous(), rc = r.contiguous();
-  const int C = x.size(-1);
-  const int rows = x.numel() / C;
+  const auto [rows, C] = rows_cols(x);
   auto y = at::empty_like(xc), sum = at::empty_like(xc);
   auto rstd = at::empty({rows}, x.options().dtype(at::kFloat));
   check_launch(orion_rmsnorm_fwd(xc.data_ptr(), w.contiguous().data_ptr(), y.data_ptr(),
@@ -867,27 +783,15 @@ std::tuple<Tensor, Tensor> rmsnorm_bwd(const Tensor& dy, const Tensor& x, const 
                                        const c10::optional<Tensor>& dw_out) {
   c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
   auto dyc = dy.contiguous(), xc = x.contiguous();
-  const int C = x.size(-1);
-  const int rows = x.numel() / C;
+  const auto [rows, C] = rows_cols(x);
   auto dx = at::empty_like(xc);
-  Tensor dw;
-  if (dw_out.has_value() && dw_out->defined()) {
-    check_grad_out(*dw_out, "dw_out");
-    TORCH_CHECK(dw_out->is_contiguous() && dw_out->numel() == C, "rmsnorm_bwd: dw_out must be C contiguous elements");
-    dw = *dw_out;
-  } else {
-    dw = at::empty({C}, w.options());
-  }
-  auto part = at::empty({((long)orion_rmsnorm_bwd_blocks(rows) + 32) * C}, x.options().dtype(at::kFloat));
+  Tensor dw = has_out(dw_out, C, "dw_out") ? *dw_out : at::empty({C}, w.options());
+  auto part = at::empty({orion_rmsnorm_bwd_scratch(rows, C)}, x.options().dtype(at::kFloat));
   Tensor drc;
-  if (dres.has_value() && dres->defined()) {
-    check_bf16(*dres, "dres");
-    drc = dres->contiguous();
-  }
+  const void* drp = opt_bf16(dres, "dres", drc);
   check_launch(orion_rmsnorm_bwd(dyc.data_ptr(), xc.data_ptr(), w.contiguous().data_ptr(),
                                  rstd.data_ptr<float>(), dx.data_ptr(), dw.data_ptr(),
-                                 part.data_ptr<float>(), rows, C,
-                                 drc.defined() ? drc.data_ptr() : nullptr, is_f32(dw) ? 1 : 0, cur_stream()),
+                                 part.data_ptr<float>(), rows, C, drp, is_f32(dw), cur_stream()),
                "rmsnorm_bwd");
   return {dx, dw};
 }
@@ -926,12 +830,9 @@ void rope_(Tensor x, const Tensor& cosv, const Tensor& sinv, int64_t pos0, doubl
 
 // ------------------------------------------------------------------ attention
 void fill_qkv(orion::AttnParams& p, const Tensor& q, const Tensor& k, const Tensor& v) {
-  p.q = (const unsigned short*)q.data_ptr();
-  p.k = (const unsigned short*)k.data_ptr();
-  p.v = (const unsigned short*)v.data_ptr();
-  p.q_sb = q.stride(0); p.q_st = q.stride(1); p.q_sh = q.stride(2);
-  p.k_sb = k.stride(0); p.k_st = k.stride(1); p.k_sh = k.stride(2);
-  p.v_sb = v.stride(0); p.v_st = v.stride(1); p.v_sh = v.stride(2);
+  set_view(p.q, p.q_sb, p.q_st, p.q_sh, q);
+  set_view(p.k, p.k_sb, p.k_st, p.k_sh, k);
+  set_view(p.v, p.v_sb, p.v_st, p.v_sh, v);
   p.B = q.size(0); p.T = q.size(1); p.Hq = q.size(2);
   p.Tk = k.size(1); p.Hkv = k.size(2);
 }
@@ -961,11 +862,10 @@ std::tuple<Tensor, Tensor> attn_fwd(const Tensor& q, const Tensor& k, const Tens
   if (causal) TORCH_CHECK(p.Tk >= p.T, "causal attention needs Tk >= T");
   auto o = at::empty({p.B, p.T, p.Hq, D}, q.options());
   auto lse = at::empty({p.B, p.Hq, p.T}, q.options().dtype(at::kFloat));
-  p.o = (unsigned short*)o.data_ptr();
-  p.o_sb = o.stride(0); p.o_st = o.stride(1); p.o_sh = o.stride(2);
+  set_view(p.o, p.o_sb, p.o_st, p.o_sh, o);
   p.lse = lse.data_ptr<float>();
   p.scale = (float)scale;
-  p.scale_log2 = (float)(scale * 1.4426950408889634);
+  p.scale_log2 = (float)(scale * LOG2E);
   check_launch(orion_attn_fwd(p, D, causal, cur_stream()), "attn_fwd");
   return {o, lse};
 }
@@ -1008,25 +908,21 @@ void attn_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor
   orion::AttnParams p{};
   fill_qkv(p, q, k, v);
   const int D = q.size(3);
-  p.o = (unsigned short*)o.data_ptr();
-  p.o_sb = o.stride(0); p.o_st = o.stride(1); p.o_sh = o.stride(2);
+  set_view(p.o, p.o_sb, p.o_st, p.o_sh, o);
   p.lse = const_cast<float*>(lse.data_ptr<float>());
   p.scale = (float)scale;
-  p.scale_log2 = (float)(scale * 1.4426950408889634);
-  p.dout = (const unsigned short*)dout.data_ptr();
-  p.do_sb = dout.stride(0); p.do_st = dout.stride(1); p.do_sh = dout.stride(2);
+  p.scale_log2 = (float)(scale * LOG2E);
+  set_view(p.dout, p.do_sb, p.do_st, p.do_sh, dout);
   auto fopts = q.options().dtype(at::kFloat);
   auto delta = at::empty({p.B, p.Hq, p.T}, fopts);
-  p.dk = (unsigned short*)dk.data_ptr();
-  p.dk_sb = dk.stride(0); p.dk_st = dk.stride(1); p.dk_sh = dk.stride(2);
-  p.dv = (unsigned short*)dv.data_ptr();
-  p.dv_sb = dv.stride(0); p.dv_st = dv.stride(1); p.dv_sh = dv.stride(2);
+  set_view(p.dk, p.dk_sb, p.dk_st, p.dk_sh, dk);
+  set_view(p.dv, p.dv_sb, p.dv_st, p.dv_sh, dv);
   p.flags = (int)flags;
   // rope_cos / rope_sin: dq and dk come out w.r.t. the UNROTATED q / k (the inverse rotation at
   // the split kernels' stores; the other forms run the rope kernel on them afterwards)
-  const bool want_rope = rope_cos.has_value() && rope_cos->defined();
+  const bool want_rope = given(rope_cos);
   if (want_rope) {
-    TORCH_CHECK(rope_sin.has_value() && rope_sin->defined(), "rope_sin missing");
+    TORCH_CHECK(given(rope_sin), "rope_sin missing");
     for (const Tensor* t : {&*rope_cos, &*rope_sin})
       TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous() && t->dim() == 2 &&
                       t->size(1) == D / 2 && t->size(0) >= rope_pos0 + std::max(p.T, p.Tk) && rope_pos0 >= 0,
@@ -1061,11 +957,10 @@ void attn_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor
                 "bias_grad needs dq / dk / dv to be views of one packed (B, T, Hq + 2 Hkv, D) dQKV");
   }
   if (attn_bwd_use_split(D, flags)) {
-    p.dq = (unsigned short*)dq.data_ptr();
-    p.dq_sb = dq.stride(0); p.dq_st = dq.stride(1); p.dq_sh = dq.stride(2);
+    set_view(p.dq, p.dq_sb, p.dq_st, p.dq_sh, dq);
     const long prow = (long)p.B * ((p.T + 31) / 32);
     if (want_bias && D == 64) {
-      bpart = at::empty({prow * ld + 16 * ld}, fopts);  // partials + the fold's scratch
+      bpart = at::empty({prow * ld + orion_colsum_mid_scratch((int)ld, 1)}, fopts);  // partials + the fold's scratch
       p.bias_part = bpart.data_ptr<float>();
       p.bias_ld = (int)ld;
     }
@@ -1146,14 +1041,12 @@ Tensor attn_decode(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache
     p.ws_ml = ws_ml.data_ptr<float>();
   }
   p.q = (const unsigned short*)q.data_ptr();
-  p.k = (const unsigned short*)k_cache.data_ptr();
-  p.v = (const unsigned short*)v_cache.data_ptr();
+  p.q_sb = q.stride(0); p.q_sh = q.stride(1);
+  set_view(p.k, p.k_sb, p.k_st, p.k_sh, k_cache);
+  set_view(p.v, p.v_sb, p.v_st, p.v_sh, v_cache);
   p.o = (unsigned short*)o.data_ptr();
   p.kv_lens = kv_lens.data_ptr<int>();
-  p.q_sb = q.stride(0); p.q_sh = q.stride(1);
-  p.k_sb = k_cache.stride(0); p.k_st = k_cache.stride(1); p.k_sh = k_cache.stride(2);
-  p.v_sb = v_cache.stride(0); p.v_st = v_cache.stride(1); p.v_sh = v_cache.stride(2);
-  p.scale_log2 = (float)(scale * 1.4426950408889634);
+  p.scale_log2 = (float)(scale * LOG2E);
   check_launch(orion_attn_decode(p, D, cur_stream()), "attn_decode");
   return o;
 }
@@ -1171,9 +1064,8 @@ Tensor kv_append(const Tensor& k_new, const Tensor& v_new, Tensor k_cache, Tenso
               "k_new / v_new must be (B, T, Hkv, D) matching the cache");
   TORCH_CHECK(k_new.device() == k_cache.device() && v_new.device() == k_cache.device(), "device mismatch");
   check_rows16(k_new, "k_new"); check_rows16(v_new, "v_new");
-  const bool has_q = q.has_value() && q->defined();
-  const bool has_rope = cosv.has_value() && cosv->defined();
-  TORCH_CHECK(has_rope == (sinv.has_value() && sinv->defined()), "kv_append: cos and sin come together");
+  const bool has_q = given(q), has_rope = given(cosv);
+  TORCH_CHECK(has_rope == given(sinv), "kv_append: cos and sin come together");
   TORCH_CHECK(!has_q || has_rope, "kv_append: q is only taken for rotation (pass cos / sin)");
   c10::hip::HIPGuardMasqueradingAsCUDA g(k_new.device());
   orion::AppendParams p{};
@@ -1199,19 +1091,14 @@ Tensor kv_append(const Tensor& k_new, const Tensor& v_new, Tensor k_cache, Tenso
     check_rows16(*q, "q");
     p.Hq = q->size(2);
     q_out = at::empty({p.B, p.T, p.Hq, p.D}, k_new.options());
-    p.q = (const unsigned short*)q->data_ptr();
+    set_view(p.q, p.q_sb, p.q_st, p.q_sh, *q);
     p.q_out = (unsigned short*)q_out.data_ptr();
-    p.q_sb = q->stride(0); p.q_st = q->stride(1); p.q_sh = q->stride(2);
   }
-  p.k_new = (const unsigned short*)k_new.data_ptr();
-  p.v_new = (const unsigned short*)v_new.data_ptr();
-  p.k_cache = (unsigned short*)k_cache.data_ptr();
-  p.v_cache = (unsigned short*)v_cache.data_ptr();
+  set_view(p.k_new, p.kn_sb, p.kn_st, p.kn_sh, k_new);
+  set_view(p.v_new, p.vn_sb, p.vn_st, p.vn_sh, v_new);
+  set_view(p.k_cache, p.kc_sb, p.kc_st, p.kc_sh, k_cache);
+  set_view(p.v_cache, p.vc_sb, p.vc_st, p.vc_sh, v_cache);
   p.kv_lens = kv_lens.data_ptr<int>();
-  p.kn_sb = k_new.stride(0); p.kn_st = k_new.stride(1); p.kn_sh = k_new.stride(2);
-  p.vn_sb = v_new.stride(0); p.vn_st = v_new.stride(1); p.vn_sh = v_new.stride(2);
-  p.kc_sb = k_cache.stride(0); p.kc_st = k_cache.stride(1); p.kc_sh = k_cache.stride(2);
-  p.vc_sb = v_cache.stride(0); p.vc_st = v_cache.stride(1); p.vc_sh = v_cache.stride(2);
   check_launch(orion_kv_append(p, cur_stream()), "kv_append");
   return q_out;
 }
@@ -1240,7 +1127,7 @@ Tensor linear_decode(const Tensor& x, const Tensor& w, const c10::optional<Tenso
   TORCH_CHECK(w.device() == x.device(), "device mismatch");
   const int64_t Nout = act == orion::LD_ACT_SWIGLU ? N / 2 : N;
   auto vec = [&](const c10::optional<Tensor>& t, int64_t n, const char* name) -> const unsigned short* {
-    if (!t.has_value() || !t->defined()) return nullptr;
+    if (!given(t)) return nullptr;
     check_bf16(*t, name);
     TORCH_CHECK(t->dim() == 1 && t->size(0) == n && t->is_contiguous() && t->device() == x.device() &&
                     (uintptr_t)t->data_ptr() % 16 == 0,
@@ -1255,7 +1142,7 @@ Tensor linear_decode(const Tensor& x, const Tensor& w, const c10::optional<Tenso
   TORCH_CHECK(norm == orion::LD_NORM_LAYER || !p.norm_b, "linear_decode: norm_bias is LayerNorm's");
   c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
   Tensor y;
-  if (out.has_value() && out->defined()) {
+  if (given(out)) {
     y = *out;
     check_bf16(y, "out");
     TORCH_CHECK(y.dim() == 2 && y.size(0) == M && y.size(1) == Nout && y.stride(1) == 1 && y.device() == x.device(),
@@ -1271,7 +1158,7 @@ Tensor linear_decode(const Tensor& x, const Tensor& w, const c10::optional<Tenso
     return a0 < b1 && b0 < a1;
   };
   TORCH_CHECK(!overlaps(x), "linear_decode: out aliases x");
-  if (residual.has_value() && residual->defined()) {
+  if (given(residual)) {
     const Tensor& r = *residual;
     check_bf16(r, "residual");
     TORCH_CHECK(r.dim() == 2 && r.size(0) == M && r.size(1) == Nout && r.stride(1) == 1 && r.device() == x.device(),
@@ -1306,7 +1193,6 @@ Tensor sample_tokens(const Tensor& logits, const Tensor& params, const c10::opti
   TORCH_CHECK(V < (1LL << 31) && B < (1LL << 31), "sample_tokens: logits too large");
   TORCH_CHECK(logits.stride(1) == 1, "sample_tokens: logits need unit stride on the vocabulary (inner stride)");
   const auto dev = logits.device();
-  auto given = [](const c10::optional<Tensor>& t) { return t.has_value() && t->defined(); };
   auto check_vec = [&](const Tensor& t, at::ScalarType ty, int64_t n, const char* name) {
     TORCH_CHECK(t.is_cuda() && t.device() == dev, "sample_tokens: ", name, " must be on the logits' device");
     TORCH_CHECK(t.scalar_type() == ty, "sample_tokens: ", name, " has the wrong dtype (", t.scalar_type(), ")");

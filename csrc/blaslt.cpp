@@ -23,6 +23,8 @@
 #include <tuple>
 #include <vector>
 
+#include "launchers.h"
+
 namespace {
 
 constexpr size_t kWorkspace = 64u << 20;

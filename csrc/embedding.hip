@@ -10,6 +10,7 @@
 // The summation order over duplicate tokens is not fixed, so deterministic mode
 // (ops/determinism.py) keeps the sort-based path.
 #include "common.h"
+#include "launchers.h"
 
 namespace orion {
 

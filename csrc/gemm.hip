@@ -25,11 +25,9 @@
 #include <cstdlib>
 
 #include "gemm_common.h"
+#include "launchers.h"
 
 using namespace orion;
-
-int orion_colsum_partials2(const float* part, float* mid, void* out, int P, int C, int f32,
-                           hipStream_t st);
 
 // Diagnostic flags (GemmArgs::flags): 4 = gemm16's stamped instantiation (EPI_STORE, the
 // stamp buffer passed as `pre`), 32 = with its stores waited for, 64 = one workgroup per work
@@ -55,8 +53,10 @@ int orion_gemm_set_diag(int flags) {
 
 // EPI_GELU_BWD with db: db[N] (fp32 when db_f32, else bf16) = column sums of the result (the
 // bias gradient) through part (orion_gemm_colsum_scratch(M, N) floats): gemm16's per-64-row
-// partials, folded by a second pass.
-int orion_gemm_colsum_scratch(int M, int N) { return ((M + 63) / 64 + 32) * N; }
+// partials, folded by a second pass (reserved like orion_colsum_scratch's: two outputs' worth).
+int orion_gemm_colsum_scratch(int M, int N) {
+  return (M + 63) / 64 * N + (int)orion_colsum_mid_scratch(N, 2);
+}
 
 // out[M][N] = X[M][K] . op(W) with op(W) = W^T for W [N][K] (wkm = 0) or W for W [K][N]
 // (wkm = 1), epilogue `epi` (GemmEpi).  Requirements (else -1): K % 64 == 0, N % 8 == 0,

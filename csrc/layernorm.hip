@@ -13,6 +13,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "launchers.h"
 
 // LN_NT: the residual stream sum (saved for the backward, read again by the next block's norm
 // several kernels later) is stored, and the far operands (the incoming residual; the saved
@@ -519,9 +520,6 @@ __global__ __launch_bounds__(NW * 64) void colsum_onepass_kernel(const float* __
 
 using namespace orion;
 
-int orion_colsum_partials2(const float* part, float* mid, void* out, int P, int C, int f32,
-                           hipStream_t st);
-
 // ORION_COLSUM=2: the two-stage column sums (A/B); default one pass
 static bool colsum_two_stage() {
   static int v = -1;
@@ -552,8 +550,6 @@ static bool ln_pick(int C, int* vec, int* iters, bool exact_fit = false) {
   }
   return *iters <= 4;
 }
-
-int orion_ln_max_cols() { return 2048; }
 
 // ORION_LN_FWD1=0: the single-input forward through the per-row kernel (A/B);
 // ORION_LN_FWD1_BLOCKS: its workgroup count (default 4096: 4 rows per wave at 65,536 rows;
@@ -614,6 +610,14 @@ int orion_layernorm_fwd(const void* x, const void* w, const void* b, void* y, fl
 int orion_layernorm_bwd_blocks(int rows) {
   int nb = (rows + 63) / 64;  // >= 64 rows (16 per wave) per workgroup
   return nb < 1024 ? (nb < 1 ? 1 : nb) : 1024;
+}
+
+// The two-stage fold writes COLSUM_SPLITS rows of C floats per output into its mid scratch.
+long orion_colsum_mid_scratch(int C, int outputs) { return (long)outputs * COLSUM_SPLITS * C; }
+
+// floats of the backward's `part`: the dw | db | dx-colsum partials, then the fold's mid scratch
+long orion_layernorm_bwd_scratch(int rows, int C) {
+  return 3 * (long)orion_layernorm_bwd_blocks(rows) * C + orion_colsum_mid_scratch(C, 3);
 }
 
 template <int VEC, int ITERS>
@@ -764,6 +768,8 @@ int orion_colsum_partials2(const float* part, float* mid, void* out, int P, int 
   return (int)hipGetLastError();
 }
 
-int orion_colsum_scratch(int rows, int C) {  // floats of scratch a colsum of `rows` rows needs
-  return (orion_layernorm_bwd_blocks(rows) + 2 * COLSUM_SPLITS) * C;
+// floats of scratch a colsum of `rows` rows needs; the single-output fold has always been
+// given two outputs' worth of mid scratch, kept so that no allocation changes size
+int orion_colsum_scratch(int rows, int C) {
+  return orion_layernorm_bwd_blocks(rows) * C + (int)orion_colsum_mid_scratch(C, 2);
 }

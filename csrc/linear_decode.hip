@@ -30,7 +30,7 @@
 //   * nothing is read beyond row M - 1, weight row N - 1 or element K - 1 (K % 8 == 0, so an
 //     8-element fragment is inside or outside as a whole); padded fragments are zeros.
 #include "common.h"
-#include "linear_decode_params.h"
+#include "launchers.h"
 
 namespace orion {
 

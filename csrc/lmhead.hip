@@ -18,6 +18,7 @@
 // The only passes left besides the three GEMMs read the (N, V / 128) partials (103 MB at
 // GPT-2's shape) and the (N, C) activations.
 #include "common.h"
+#include "launchers.h"
 
 namespace orion {
 

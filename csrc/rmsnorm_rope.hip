@@ -11,6 +11,7 @@
 // projection), output contiguous; cos/sin come from a host-built fp32 table
 // (T, D/2) -- no device transcendental per element (HIP guide Appendix B).
 #include "common.h"
+#include "launchers.h"
 
 // RMS_NT: the backward loads its saved input (read once, long after it was written) with the
 // non-temporal hint: rms_bwd 89.3 vs 93.8 us at Llama-7B shapes; the same on the forward's
@@ -197,9 +198,6 @@ __global__ __launch_bounds__(256) void rope_kernel(const bf16_t* x, long xsb, lo
 
 using namespace orion;
 
-int orion_colsum_partials2(const float* part, float* mid, void* out, int P, int C, int f32,
-                           hipStream_t st);
-
 static int rms_blocks(int rows) { return rows < 1024 ? rows : 1024; }
 
 int orion_rmsnorm_fwd(const void* x, const void* w, void* y, float* rstd, int rows, int C,
@@ -219,6 +217,12 @@ int orion_rmsnorm_fwd(const void* x, const void* w, void* y, float* rstd, int ro
 }
 
 int orion_rmsnorm_bwd_blocks(int rows) { return rms_blocks(rows); }
+
+// floats of `part` below: one row of partials per workgroup, then the fold's mid scratch
+// (reserved like orion_colsum_scratch's: two outputs' worth)
+long orion_rmsnorm_bwd_scratch(int rows, int C) {
+  return (long)rms_blocks(rows) * C + orion_colsum_mid_scratch(C, 2);
+}
 
 int orion_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rstd, void* dx,
                       void* dw, float* part, int rows, int C, const void* dres, int dw_f32,

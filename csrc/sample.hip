@@ -34,7 +34,7 @@
 #include <limits.h>
 
 #include "common.h"
-#include "sample_params.h"
+#include "launchers.h"
 
 namespace orion {
 

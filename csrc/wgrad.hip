@@ -20,6 +20,7 @@
 //   * LDS-DMA staging into a 4-deep ring (see the kernel comment), one raw barrier
 //     per stage.
 #include "gemm_common.h"
+#include "launchers.h"
 
 namespace orion {
 
@@ -220,8 +221,6 @@ int orion_wgrad_splits(int M, int N1, int N2) {
 // 6 rows at S2 = 2 -- 5.5 instead of 6 item times.  GPT-2's LM head (50,304 x 768: 591
 // tiles, 2.3 rounds, round 5): 170 rows unsplit (510 tiles) + 26.5 rows at S2 = 3 -- 2.33
 // instead of 3 item times.  Returns R1 (0: no split) and S2.
-int orion_wgrad_effective_splits(int M, int S);
-
 int orion_wgrad_tail_rows(int M, int N1, int N2, int* S2) {
   *S2 = 1;
   if (orion_wgrad_splits(M, N1, N2) != 1) return 0;

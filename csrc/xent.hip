@@ -10,6 +10,7 @@
 // The caller (``ops/xent.py``) multiplies by the upstream gradient afterwards
 // on the much smaller GEMM outputs.
 #include "common.h"
+#include "launchers.h"
 #include "mfma_lds.h"
 
 // cache-policy bits of the row's buffer loads / stores (A/B builds: -DXENT_LD_AUX=..)

@@ -3,25 +3,11 @@
 // argument validation that must reject a bad call BEFORE anything is launched.  Built by
 // tests/test_native_host_sanitizers.py with the sanitizers on the host side only
 // (hipcc -Xarch_host -fsanitize=...); no kernel is launched, so no GPU is needed.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
-int orion_wgrad_splits(int M, int N1, int N2);
-int orion_wgrad_effective_splits(int M, int S);
-int orion_wgrad_tail_rows(int M, int N1, int N2, int* S2);
-int orion_wgrad(const void*, long, const void*, long, int, int, int, int, float*, void*,
-                const float*, int, int, int, hipStream_t);
-int orion_gemm(const void*, long, const void*, long, int, int, int, int, int, void*, long,
-               const void*, void*, long, const void*, long, hipStream_t, void* db = nullptr,
-               int db_f32 = 0, float* part = nullptr);
-int orion_gemm_colsum_scratch(int M, int N);
-int orion_layernorm_bwd_blocks(int rows);
-int orion_colsum_scratch(int rows, int C);
-int orion_rmsnorm_bwd_blocks(int rows);
+#include "launchers.h"
 
 static int failures = 0;
 #define CHECK(cond)                                                       \
@@ -77,6 +63,17 @@ int main() {
     CHECK(orion_rmsnorm_bwd_blocks(rows) >= 1);
     CHECK(orion_colsum_scratch(rows, 768) >= 768);
   }
+  // the exported scratch sizes are, to the float, the expressions their callers used to write out
+  // (the fold's mid scratch as literal multiples of its 16 splits)
+  for (int rows : {1, 63, 64, 65, 4096, 65536, 70000})
+    for (int C : {64, 768, 4096}) {
+      const long nb = orion_layernorm_bwd_blocks(rows), rb = orion_rmsnorm_bwd_blocks(rows);
+      const long prow = rows, ld = C;  // attn_bwd's bias partials: prow 32-token blocks of ld columns
+      CHECK(orion_layernorm_bwd_scratch(rows, C) == 3 * nb * C + 48L * C);
+      CHECK(orion_rmsnorm_bwd_scratch(rows, C) == (rb + 32) * C);
+      CHECK(orion_colsum_scratch(rows, C) == (nb + 32) * C);
+      CHECK(prow * ld + orion_colsum_mid_scratch((int)ld, 1) == prow * ld + 16 * ld);
+    }
   // argument validation: every one of these must be rejected without a launch
   std::vector<uint16_t> buf(1 << 16);
   const void* p = buf.data();
