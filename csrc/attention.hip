@@ -44,6 +44,7 @@
 
 #include "common.h"
 #include "launchers.h"
+#include "lds_once.h"
 #include "mfma_lds.h"
 
 namespace orion {
@@ -253,12 +254,6 @@ __global__ __launch_bounds__(256) void attn_bwd_pre_kernel(AttnParams p, float* 
 }
 
 // ============================================================================ backward
-// waves (x 32 keys) per backward workgroup.  8 waves (256 keys) halve the dQ atomics
-// but measured 7 % slower at D = 64 on MI355X (8-wave barriers, more idle waves on the
-// causal diagonal), and do not fit LDS at D = 128: 4 everywhere.
-template <int D>
-__host__ __device__ constexpr int bwd_waves() { return 4; }
-
 template <int D, bool CAUSAL>
 __global__ __launch_bounds__(bwd_waves<D>() * 64, (D == 64 ? 2 : 1)) void attn_bwd_kernel(AttnParams p) {
   constexpr int NW = bwd_waves<D>(), NT = NW * 64;
@@ -542,76 +537,23 @@ using namespace orion;
 
 extern "C++" {
 
-static size_t fwd_lds(int D) { return (size_t)2 * 2 * 64 * D * 2; }
-static size_t bwd_lds(int D) {
-  const size_t nw = D == 64 ? bwd_waves<64>() : bwd_waves<128>();
-  return 32 * nw * D * 2 + 4 * 32 * D * 2 + nw * 32 * 32 * 2 + 128 * 4 + nw * D * (32 + 4) * 4;
+// the 64-bit-addressed forward: past 2 GB of K / V, or ORION_ATTN_FWD=v2 (csrc/attn_plan.h)
+int orion_attn_fwd64(const AttnLaunch& l, const AttnParams& p, int D, bool causal, hipStream_t st) {
+  return attn_dispatch(D, causal, [&](auto d, auto c) {
+    return launch_dynamic_lds<attn_fwd_kernel<d(), c()>>(l.grid, l.block, l.lds, st, p);
+  });
 }
 
-template <int D, bool CAUSAL>
-static void set_lds_attr() {
-  static bool done = false;
-  if (!done) {
-    hipFuncSetAttribute((const void*)attn_fwd_kernel<D, CAUSAL>,
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)fwd_lds(D));
-    hipFuncSetAttribute((const void*)attn_bwd_kernel<D, CAUSAL>,
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)bwd_lds(D));
-    done = true;
-  }
-}
-
-// ORION_ATTN_FWD=v2 selects the kernel below (A/B measurement); default: attn_fwd.hip
-static bool fwd_v2() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("ORION_ATTN_FWD");
-    v = (e && e[0] == 'v' && e[1] == '2') ? 1 : 0;
-  }
-  return v == 1;
-}
-
-int orion_attn_fwd(const AttnParams& p, int D, bool causal, hipStream_t st) {
-  if (!fwd_v2()) {
-    const int r = orion_attn_fwd3(p, D, causal, st);
-    if (r != -2) return r;  // -2: offsets beyond 2 GB, the kernel below addresses 64-bit
-  }
-  const int BM = 128;
-  const int grid = ((p.T + BM - 1) / BM) * p.B * p.Hq;
-#define FWD(DD, CC)                                                                 \
-  set_lds_attr<DD, CC>();                                                           \
-  attn_fwd_kernel<DD, CC><<<grid, 256, fwd_lds(DD), st>>>(p);
-  if (D == 64) {
-    if (causal) { FWD(64, true) } else { FWD(64, false) }
-  } else if (D == 128) {
-    if (causal) { FWD(128, true) } else { FWD(128, false) }
-  } else {
-    return -1;
-  }
-#undef FWD
-  return (int)hipGetLastError();
-}
-
-int orion_attn_bwd(const AttnParams& p, int D, bool causal, float* delta, hipStream_t st) {
-  const long rows = (long)p.B * p.Hq * p.T;
-  const long threads = rows * (D / 8);
-  const int pre_grid = (int)((threads + 255) / 256);
-  if (D == 64) attn_bwd_pre_kernel<64><<<pre_grid, 256, 0, st>>>(p, delta);
-  else if (D == 128) attn_bwd_pre_kernel<128><<<pre_grid, 256, 0, st>>>(p, delta);
-  else return -1;
+int orion_attn_bwd(const AttnBwdPlan& plan, const AttnParams& p, int D, bool causal, float* delta,
+                   hipStream_t st) {
+  if (plan.form != ATTN_FUSED) return -1;  // step 0: attn_bwd_pre, step 1: attn_bwd
   AttnParams q = p;
   q.delta = delta;
-#define BWD(DD, CC)                                                                 \
-  set_lds_attr<DD, CC>();                                                           \
-  attn_bwd_kernel<DD, CC><<<((p.Tk + 32 * bwd_waves<DD>() - 1) / (32 * bwd_waves<DD>())) * \
-                                p.B * p.Hkv,                                        \
-                            64 * bwd_waves<DD>(), bwd_lds(DD), st>>>(q);
-  if (D == 64) {
-    if (causal) { BWD(64, true) } else { BWD(64, false) }
-  } else {
-    if (causal) { BWD(128, true) } else { BWD(128, false) }
-  }
-#undef BWD
-  return (int)hipGetLastError();
+  const AttnLaunch &pre = plan.step[0], &bwd = plan.step[1];
+  return attn_dispatch(D, causal, [&](auto d, auto c) {
+    attn_bwd_pre_kernel<d()><<<pre.grid, pre.block, pre.lds, st>>>(q, delta);
+    return launch_dynamic_lds<attn_bwd_kernel<d(), c()>>(bwd.grid, bwd.block, bwd.lds, st, q);
+  });
 }
 
 int orion_attn_dq_convert(const float* acc, void* dq, long sb, long st_, long sh, int B, int Hq,

@@ -26,12 +26,11 @@
 //                  bf16 dQ written once -- no fp32 accumulator, no conversion pass.
 //
 // MFMA v_mfma_f32_32x32x16_bf16 throughout; LDS images and fragment helpers: mfma_lds.h.
-#include <cstdlib>
-#include <cstring>
 #include <type_traits>
 
 #include "common.h"
 #include "launchers.h"
+#include "lds_once.h"
 #include "mfma_lds.h"
 
 namespace orion {
@@ -175,15 +174,13 @@ ORION_DEVICE void store_row_grad(const f32x16 (&acc)[NDB], float sc, bf16_t* __r
 }
 
 // ============================================================================ dK / dV
-// NW waves x 32 keys per workgroup; query tiles of 32 rows double-buffered in LDS
+// NW = kv_waves<D>() (csrc/attn_plan.h) waves x 32 keys per workgroup; query tiles of 32 rows double-buffered in LDS
 // (register staged: the next tile's loads are issued before this tile's MFMAs and written
 // after them).  One LDS barrier per tile.  Two workgroups per CU (two waves per SIMD, so
 // one wave's MFMAs overlap the other's softmax / LDS phase): at D = 128 that fits the
 // 256-register budget only with the K fragments read from an LDS image per query tile
 // (KLDS) instead of held in registers (25 spilled registers otherwise).
-template <int D>
-__host__ __device__ constexpr int kv_waves() { return 4; }
-
+//
 // STAMPS (diagnostic instantiation, ORION_ATTN_DIAG=1, D = 64): every wave accumulates
 // s_memtime deltas of the five phases of a query tile (S/dP chain issue, softmax, dV/dK
 // issue, LDS stage write, barrier) and writes them with its active-tile count and lifetime
@@ -896,153 +893,39 @@ using namespace orion;
 
 extern "C++" {
 
-static size_t kv_lds(int D) {
-  return (size_t)2 * 2 * 32 * D * 2 + 4 * 32 * 4 + (D == 128 ? (size_t)32 * 4 * D * 2 : 0);
-}
-static size_t dq_lds(int D) { return (size_t)2 * 2 * 64 * D * 2; }
-
-template <int D, bool CAUSAL>
-static void kv_launch(const AttnParams& q, int grid, hipStream_t st) {
-  static bool done = false;
-  if (!done) {
-    (void)hipFuncSetAttribute((const void*)attn_bwd_kv_kernel<D, CAUSAL>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kv_lds(D));
-    done = true;
-  }
-  attn_bwd_kv_kernel<D, CAUSAL><<<grid, kv_waves<D>() * 64, kv_lds(D), st>>>(q);
-}
-
-// ORION_ATTN_DQ=v3: the D = 64 dQ kernel of rounds 2-4 (A/B); default attn_bwd_dq4
-static bool dq_v3() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("ORION_ATTN_DQ");
-    v = (e && strcmp(e, "v3") == 0) ? 1 : 0;
-  }
-  return v == 1;
-}
-
-template <bool CAUSAL, bool BIAS>
-static void dq4_launch(const AttnParams& q, int grid, hipStream_t st) {
-  static bool done = false;
-  if (!done) {
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dq4_kernel<CAUSAL, BIAS>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * 64 * 64 * 2);
-    done = true;
-  }
-  attn_bwd_dq4_kernel<CAUSAL, BIAS><<<grid, 256, 2 * 2 * 64 * 64 * 2, st>>>(q);
-}
-
-template <int D, bool CAUSAL, bool BIAS = false, bool FD = false>
-static void dq_launch(const AttnParams& q, int grid, hipStream_t st) {
-  static bool done = false;
-  if (!done) {
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<D, CAUSAL, BIAS, FD>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)dq_lds(D));
-    done = true;
-  }
-  attn_bwd_dq_kernel<D, CAUSAL, BIAS, FD><<<grid, 256, dq_lds(D), st>>>(q);
-}
-
-// ORION_ATTN_DELTA=pass: the separate delta pass at D = 128 (A/B); default: fused into dQ
-static bool delta_pass() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("ORION_ATTN_DELTA");
-    v = (e && strcmp(e, "pass") == 0) ? 1 : 0;
-  }
-  return v == 1;
-}
-
-// delta (caller-allocated [B][Hq][T] fp32 scratch), dK/dV and dQ; p.dq / dk / dv are bf16
-// outputs (strided views allowed).  Order on stream st: D = 64 -- dQ (attn_bwd_dq4, writes
-// delta and the bias K / V columns), then dK/dV (reads delta); D = 128 -- dQ (attn_bwd_dq with
-// the fused delta), then dK/dV; ORION_ATTN_DQ=v3 / ORION_ATTN_DELTA=pass -- the delta pass,
-// dK/dV, dQ.
-int orion_attn_bwd_split(const AttnParams& p, int D, bool causal, float* delta, hipStream_t st) {
-  // 32-bit buffer offsets: the dQ kernel addresses one (batch, KV head)'s K / V, the dK/dV
-  // kernel one batch's Q / dO over all query heads; beyond 2 GB the caller takes the fused
-  // form (64-bit addressing)
-  constexpr long LIM = 1L << 31;
-  if (((long)(p.Tk - 1) * p.k_st + D) * 2 >= LIM || ((long)(p.Tk - 1) * p.v_st + D) * 2 >= LIM ||
-      ((long)(p.T - 1) * p.q_st + (long)(p.Hq - 1) * p.q_sh + D) * 2 >= LIM ||
-      ((long)(p.T - 1) * p.do_st + (long)(p.Hq - 1) * p.do_sh + D) * 2 >= LIM)
-    return -2;
-  const long rows = (long)p.B * p.Hq * p.T;
-  const int pre_grid = (int)((rows * (D / 8) + 255) / 256);
+// The steps of a split plan (csrc/attn_plan.h), in order on stream st.  delta: caller-allocated
+// [B][Hq][T] fp32 scratch; p.dq / dk / dv are bf16 outputs (strided views allowed).
+int orion_attn_bwd_split(const AttnBwdPlan& plan, const AttnParams& p, int D, bool causal, float* delta,
+                         hipStream_t st) {
   AttnParams q = p;
   q.delta = delta;
-  const int kv_grid = ((p.Tk + 32 * 4 - 1) / (32 * 4)) * p.B * p.Hkv;
-  const int dq_grid = ((p.T + 127) / 128) * p.B * p.Hq;
-  static const bool diag = getenv("ORION_ATTN_DIAG") && getenv("ORION_ATTN_DIAG")[0] == '1';
-  if (diag && D == 64) {  // stamped dK/dV kernel only, stamps over p.dq (scripts/attn_stamps.py)
-    attn_delta_kernel<64><<<pre_grid, 256, 0, st>>>(p, delta);
-    if (causal) {
-      (void)hipFuncSetAttribute((const void*)attn_bwd_kv_kernel<64, true, true>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kv_lds(64));
-      attn_bwd_kv_kernel<64, true, true><<<kv_grid, kv_waves<64>() * 64, kv_lds(64), st>>>(q);
-    } else {
-      (void)hipFuncSetAttribute((const void*)attn_bwd_kv_kernel<64, false, true>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kv_lds(64));
-      attn_bwd_kv_kernel<64, false, true><<<kv_grid, kv_waves<64>() * 64, kv_lds(64), st>>>(q);
-    }
-    return (int)hipGetLastError();
-  }
-  // D = 64 (attn_bwd_dq4): the dQ kernel first -- it computes delta (and, with the QKV bias,
-  // the K / V bias columns) in its prologue -- then dK/dV, which reads delta.  Otherwise (and
-  // with ORION_ATTN_DQ=v3): the delta pass, dK/dV, dQ.
-  const bool dq4 = D == 64 && !dq_v3();
-  if (p.bias_part) {  // packed self-attention with the QKV bias gradient (GPT-2: D = 64, MHA)
-    if (D != 64 || p.T != p.Tk || p.Hq != p.Hkv || p.T % 32) return -3;
-    if (dq4) {
-      if (causal) {
-        dq4_launch<true, true>(q, dq_grid, st);
-        kv_launch<64, true>(q, kv_grid, st);
-      } else {
-        dq4_launch<false, true>(q, dq_grid, st);
-        kv_launch<64, false>(q, kv_grid, st);
+  return attn_dispatch(D, causal, [&](auto d, auto c) {
+    constexpr int DD = d();
+    constexpr bool C = c();
+    auto step = [&](const AttnLaunch& l) {
+      const int g = l.grid, b = l.block, lds = l.lds;
+      switch (l.kernel) {
+        case ATTN_DELTA: return launch_dynamic_lds<attn_delta_kernel<DD>>(g, b, lds, st, q, delta);
+        case ATTN_KV: return launch_dynamic_lds<attn_bwd_kv_kernel<DD, C>>(g, b, lds, st, q);
+        case ATTN_DQ: return launch_dynamic_lds<attn_bwd_dq_kernel<DD, C>>(g, b, lds, st, q);
       }
-      return (int)hipGetLastError();
-    }
-#define SPLITB(CC)                                                                                  \
-  attn_delta_kernel<64, true><<<pre_grid, 256, 0, st>>>(q, delta);                                  \
-  kv_launch<64, CC>(q, kv_grid, st);                                                                \
-  dq_launch<64, CC, true>(q, dq_grid, st);
-    if (causal) { SPLITB(true) } else { SPLITB(false) }
-#undef SPLITB
-    return (int)hipGetLastError();
-  }
-  if (dq4) {
-    if (causal) {
-      dq4_launch<true, false>(q, dq_grid, st);
-      kv_launch<64, true>(q, kv_grid, st);
-    } else {
-      dq4_launch<false, false>(q, dq_grid, st);
-      kv_launch<64, false>(q, kv_grid, st);
-    }
-    return (int)hipGetLastError();
-  }
-#define SPLIT(DD, CC)                                    \
-  attn_delta_kernel<DD><<<pre_grid, 256, 0, st>>>(p, delta); \
-  kv_launch<DD, CC>(q, kv_grid, st);                       \
-  dq_launch<DD, CC>(q, dq_grid, st);
-  if (D == 64) {
-    if (causal) { SPLIT(64, true) } else { SPLIT(64, false) }
-  } else if (D == 128 && !delta_pass()) {  // dQ first: it writes delta for dK/dV
-    if (causal) {
-      dq_launch<128, true, false, true>(q, dq_grid, st);
-      kv_launch<128, true>(q, kv_grid, st);
-    } else {
-      dq_launch<128, false, false, true>(q, dq_grid, st);
-      kv_launch<128, false>(q, kv_grid, st);
-    }
-  } else if (D == 128) {
-    if (causal) { SPLIT(128, true) } else { SPLIT(128, false) }
-  } else {
-    return -1;
-  }
-#undef SPLIT
-  return (int)hipGetLastError();
+      if constexpr (DD == 64) {
+        switch (l.kernel) {
+          case ATTN_DELTA_BIAS: return launch_dynamic_lds<attn_delta_kernel<64, true>>(g, b, lds, st, q, delta);
+          case ATTN_KV_STAMPED: return launch_dynamic_lds<attn_bwd_kv_kernel<64, C, true>>(g, b, lds, st, q);
+          case ATTN_DQ_BIAS: return launch_dynamic_lds<attn_bwd_dq_kernel<64, C, true>>(g, b, lds, st, q);
+          case ATTN_DQ4: return launch_dynamic_lds<attn_bwd_dq4_kernel<C, false>>(g, b, lds, st, q);
+          case ATTN_DQ4_BIAS: return launch_dynamic_lds<attn_bwd_dq4_kernel<C, true>>(g, b, lds, st, q);
+        }
+      } else if (l.kernel == ATTN_DQ_FD) {
+        return launch_dynamic_lds<attn_bwd_dq_kernel<128, C, false, true>>(g, b, lds, st, q);
+      }
+      return -1;  // no such kernel for this (D, causal)
+    };
+    for (int i = 0; i < plan.n; ++i)
+      if (const int rc = step(plan.step[i])) return rc;
+    return 0;
+  });
 }
 
 }  // extern "C++"

@@ -22,11 +22,11 @@
 // in LDS, two workgroups per CU.  bf16 in / out, fp32 accumulation, O written as (B, T, H,
 // D), lse in base 2.  attention.hip's older forward remains the 64-bit-addressed fallback
 // (offsets past 2 GB; ORION_ATTN_FWD=v2 forces it for its test).
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
 #include "launchers.h"
+#include "lds_once.h"
 #include "mfma_lds.h"
 
 #ifndef ATTN_FWD_QB64
@@ -562,89 +562,29 @@ using namespace orion;
 
 extern "C++" {
 
-template <int D, bool CAUSAL, int QB>
-static void fwd3_attr() {
-  static bool done = false;
-  if (!done) {
-    (void)hipFuncSetAttribute((const void*)attn_fwd3_kernel<D, CAUSAL, QB>,
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * 64 * D * 2);
-    done = true;
-  }
-}
-
-template <bool CAUSAL>
-static void fwd4_launch(const AttnParams& p, hipStream_t st) {
-  static bool done = false;
-  if (!done) {
-    (void)hipFuncSetAttribute((const void*)attn_fwd4_kernel<CAUSAL>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              2 * 2 * 64 * 64 * 2);
-    done = true;
-  }
-  attn_fwd4_kernel<CAUSAL><<<((p.T + 127) / 128) * p.B * p.Hq, 256, 2 * 2 * 64 * 64 * 2, st>>>(p);
-}
-
-// ORION_ATTN_FWD=v3: the D = 64 forward of rounds 3-4 (A/B); default attn_fwd4
-static bool fwd_v3() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("ORION_ATTN_FWD");
-    v = (e && e[0] == 'v' && e[1] == '3') ? 1 : 0;
-  }
-  return v == 1;
-}
-
-template <int D, bool CAUSAL>
-static void fwd3_launch(const AttnParams& p, int qb64, size_t lds, hipStream_t st) {
-  if constexpr (D == 64 && CAUSAL) {
-    static const bool diag = getenv("ORION_ATTN_FWD_DIAG") && getenv("ORION_ATTN_FWD_DIAG")[0] == '1';
-    if (diag) {  // stamped instantiation: phase sums over p.o (scripts/attn_fwd_stamps.py)
-      (void)hipFuncSetAttribute((const void*)attn_fwd3_kernel<64, true, 2, true>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * 64 * D * 2);
-      attn_fwd3_kernel<64, true, 2, true><<<((p.T + 255) / 256) * p.B * p.Hq, 256, lds, st>>>(p);
-      return;
-    }
-  }
-  if constexpr (D == 64) {
-    static const bool diag = getenv("ORION_ATTN_FWD_DIAG") && getenv("ORION_ATTN_FWD_DIAG")[0] == '1';
-    if constexpr (CAUSAL) {  // the non-causal form runs out of registers at 4 waves: fwd3
-      if (!diag && !fwd_v3()) {
-        fwd4_launch<CAUSAL>(p, st);
-        return;
+// D = 64: two 32-row query blocks per wave (one K / V fragment read for both, the two
+// softmax chains interleaved with each other's MFMAs; 255 VGPRs) -- equal in isolation to one
+// block per wave but faster in the whole GPT-2 step in 8 of 8 alternating pairs on two boxes
+// (+0.2-0.6 %, profiles/ab/ab_fwd_qb*.log); D = 128: one block per wave.
+int orion_attn_fwd(const AttnParams& p, int D, bool causal, hipStream_t st) {
+  const AttnLaunch l = attn_fwd_plan(p, D, causal, attn_switches(), ATTN_FWD_QB64);
+  if (l.kernel < 0) return l.kernel;
+  if (l.kernel == ATTN_FWD64) return orion_attn_fwd64(l, p, D, causal, st);
+  return attn_dispatch(D, causal, [&](auto d, auto c) {
+    constexpr int DD = d();
+    constexpr bool C = c();
+    if (l.kernel == ATTN_FWD3_QB1) return launch_dynamic_lds<attn_fwd3_kernel<DD, C, 1>>(l.grid, l.block, l.lds, st, p);
+    if constexpr (DD == 64) {
+      if (l.kernel == ATTN_FWD3_QB2)
+        return launch_dynamic_lds<attn_fwd3_kernel<64, C, 2>>(l.grid, l.block, l.lds, st, p);
+      if constexpr (C) {
+        if (l.kernel == ATTN_FWD4) return launch_dynamic_lds<attn_fwd4_kernel<true>>(l.grid, l.block, l.lds, st, p);
+        if (l.kernel == ATTN_FWD3_STAMPED)  // phase sums over p.o (scripts/attn_fwd_stamps.py)
+          return launch_dynamic_lds<attn_fwd3_kernel<64, true, 2, true>>(l.grid, l.block, l.lds, st, p);
       }
     }
-  }
-  if constexpr (D == 64) {
-    if (qb64 == 2) {
-      fwd3_attr<D, CAUSAL, 2>();
-      attn_fwd3_kernel<D, CAUSAL, 2><<<((p.T + 255) / 256) * p.B * p.Hq, 256, lds, st>>>(p);
-      return;
-    }
-  }
-  fwd3_attr<D, CAUSAL, 1>();
-  attn_fwd3_kernel<D, CAUSAL, 1><<<((p.T + 127) / 128) * p.B * p.Hq, 256, lds, st>>>(p);
-}
-
-// returns -1 for an unsupported head dim, -2 when the buffer-offset range is exceeded
-// (the caller falls back to the older kernel)
-int orion_attn_fwd3(const AttnParams& p, int D, bool causal, hipStream_t st) {
-  const long kbytes = ((long)(p.Tk - 1) * p.k_st + D) * 2, vbytes = ((long)(p.Tk - 1) * p.v_st + D) * 2;
-  if (kbytes >= (1L << 31) || vbytes >= (1L << 31)) return -2;
-  const size_t lds = (size_t)2 * 2 * 64 * D * 2;
-  // D = 64: two 32-row query blocks per wave (one K / V fragment read for both, the two
-  // softmax chains interleaved with each other's MFMAs; 255 VGPRs) -- equal in isolation to one
-  // block per wave but faster in the whole GPT-2 step in 8 of 8 alternating pairs on two boxes
-  // (+0.2-0.6 %, profiles/ab/ab_fwd_qb*.log); D = 128: one block per wave.
-  constexpr int qb64 = ATTN_FWD_QB64;
-#define FWD3(DD, CC) fwd3_launch<DD, CC>(p, qb64, lds, st);
-  if (D == 64) {
-    if (causal) { FWD3(64, true) } else { FWD3(64, false) }
-  } else if (D == 128) {
-    if (causal) { FWD3(128, true) } else { FWD3(128, false) }
-  } else {
-    return -1;
-  }
-#undef FWD3
-  return (int)hipGetLastError();
+    return -1;  // no such kernel for this (D, causal)
+  });
 }
 
 }  // extern "C++"

@@ -1,4 +1,5 @@
-// Parameter block shared by csrc/attention.hip and csrc/bindings.cpp.
+// Parameter block of the attention kernels (csrc/attention.hip, attn_fwd.hip, attn_bwd_split.hip), filled by
+// csrc/bindings.cpp and read by the launch plans of csrc/attn_plan.h.
 #pragma once
 
 namespace orion {
@@ -27,7 +28,9 @@ struct AttnParams {
   long dv_sb, dv_st, dv_sh;
   unsigned short* dq;  // bf16 dQ (split backward: written directly, no fp32 accumulator)
   long dq_sb, dq_st, dq_sh;
-  int flags;  // 1 = skip dQ atomics (diagnostic), 4 = deterministic (split backward), 8 = fused
+  // attn_bwd's flags.  The kernels read bit 0 only (fused backward: skip the dQ atomics, a diagnostic);
+  // bits 2 (deterministic: split form) and 3 (fused form) choose the form in attn_bwd_plan
+  int flags;
   // split backward, packed self-attention (T == Tk, MHA, D = 64, T % 32 == 0): column sums of
   // dQ | dK | dV over every 32-token block, [B * T / 32][bias_ld] fp32 (bias_ld = 3 Hq D) -- dQ's
   // from the dQ kernel, dK's (identically 0) and dV's (= those of dO) from the delta pass -- so

@@ -870,23 +870,18 @@ std::tuple<Tensor, Tensor> attn_fwd(const Tensor& q, const Tensor& k, const Tens
   return {o, lse};
 }
 
-// Backward form: "split" (csrc/attn_bwd_split.hip: dK/dV and dQ kernels, no atomics,
-// deterministic) always, except for operands whose 32-bit buffer offsets overflow (one batch's
-// Q / dO or one KV head's K / V beyond 2 GB): those take the 64-bit-addressed fused kernel of
+// Backward form (decided by csrc/attn_plan.h): "split" (csrc/attn_bwd_split.hip: dK/dV and dQ kernels,
+// no atomics, deterministic) always, except for operands whose 32-bit buffer offsets overflow (one
+// batch's Q / dO or one KV head's K / V beyond 2 GB): those take the 64-bit-addressed fused kernel of
 // csrc/attention.hip (one pass, fp32-atomic dQ; split measured faster wherever both run:
 // 0.632 vs 0.722 ms at B64 T1024 H12 D64, 3.39 vs 4.46 ms at B4 T4096 H32/8 D128).  flags bit 2
-// (deterministic) forces split; bit 3 forces the large-operand fallback (its test only).
+// (deterministic) asks for split; bit 3 forces the large-operand fallback (its test only).
 // column sums of the packed bf16 dQKV starting at dq ([rows][ld], contiguous)
 void attn_bias_colsum_packed(const Tensor& dq, const Tensor& out, long rows, long ld) {
   auto part = at::empty({(long)orion_colsum_scratch((int)rows, (int)ld)}, dq.options().dtype(at::kFloat));
   check_launch(orion_colsum_bf16(dq.data_ptr(), out.data_ptr(), part.data_ptr<float>(), (int)rows, (int)ld,
                                  is_f32(out), cur_stream()),
                "attn_bias_colsum");
-}
-
-bool attn_bwd_use_split(int D, int64_t flags) {
-  if (flags & 4) return true;
-  return !(flags & 8);  // bit 3: the large-operand fallback's test
 }
 
 // dq/dk/dv: preallocated outputs (may be strided views of one packed buffer)
@@ -946,7 +941,6 @@ void attn_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor
   };
   const long ld = (long)(p.Hq + 2 * p.Hkv) * D;
   const bool want_bias = has_out(bias_grad, ld, "bias_grad");
-  Tensor bpart;
   if (want_bias) {
     const long e = dq.element_size();
     TORCH_CHECK(p.T == p.Tk && dq.stride(1) == ld && dk.stride(1) == ld && dv.stride(1) == ld &&
@@ -956,42 +950,34 @@ void attn_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor
                     (char*)dv.data_ptr() == (char*)dk.data_ptr() + p.Hkv * D * e,
                 "bias_grad needs dq / dk / dv to be views of one packed (B, T, Hq + 2 Hkv, D) dQKV");
   }
-  if (attn_bwd_use_split(D, flags)) {
-    set_view(p.dq, p.dq_sb, p.dq_st, p.dq_sh, dq);
-    const long prow = (long)p.B * ((p.T + 31) / 32);
-    if (want_bias && D == 64) {
-      bpart = at::empty({prow * ld + orion_colsum_mid_scratch((int)ld, 1)}, fopts);  // partials + the fold's scratch
-      p.bias_part = bpart.data_ptr<float>();
-      p.bias_ld = (int)ld;
-    }
-    int rc = orion_attn_bwd_split(p, D, causal, delta.data_ptr<float>(), cur_stream());
-    if (rc == -3) {  // no in-kernel column sums for this form: plain kernels, summed below
-      p.bias_part = nullptr;
-      rc = orion_attn_bwd_split(p, D, causal, delta.data_ptr<float>(), cur_stream());
-    }
-    if (rc != -2) {  // -2: operands beyond the split kernels' 32-bit offsets -> fused form
-      check_launch(rc, "attn_bwd_split");
-      if (want_bias) {
-        if (p.bias_part)
-          check_launch(orion_colsum_partials2(p.bias_part, p.bias_part + prow * ld, bias_grad->data_ptr(),
-                                              (int)prow, (int)ld, is_f32(*bias_grad), cur_stream()),
-                       "attn_bias_colsum");
-        else
-          attn_bias_colsum_packed(dq, *bias_grad, p.B * p.T, ld);
-      }
-      return;
-    }
-    p.bias_part = nullptr;
+  const orion::AttnBwdPlan plan = orion::attn_bwd_plan(p, D, causal, (int)flags, want_bias, orion::attn_switches());
+  const bool split = plan.form == orion::ATTN_SPLIT;
+  const long prow = (long)p.B * ((p.T + 31) / 32);
+  Tensor bpart;
+  if (plan.bias_in_kernel) {
+    bpart = at::empty({prow * ld + orion_colsum_mid_scratch((int)ld, 1)}, fopts);  // partials + the fold's scratch
+    p.bias_part = bpart.data_ptr<float>();
+    p.bias_ld = (int)ld;
   }
-  p.rope_cos = p.rope_sin = nullptr;
-  auto dq_acc = at::empty({p.B, p.Hq, p.T, D}, fopts);
-  p.dq_acc = dq_acc.data_ptr<float>();
-  check_launch(orion_attn_bwd(p, D, causal, delta.data_ptr<float>(), cur_stream()), "attn_bwd");
-  check_launch(orion_attn_dq_convert(dq_acc.data_ptr<float>(), dq.data_ptr(), dq.stride(0),
-                                     dq.stride(1), dq.stride(2), p.B, p.Hq, p.T, D, cur_stream()),
-               "attn_dq_convert");
-  if (want_bias) attn_bias_colsum_packed(dq, *bias_grad, p.B * p.T, ld);
-  unrope();
+  if (split) {
+    set_view(p.dq, p.dq_sb, p.dq_st, p.dq_sh, dq);
+    check_launch(orion_attn_bwd_split(plan, p, D, causal, delta.data_ptr<float>(), cur_stream()), "attn_bwd_split");
+  } else {
+    p.rope_cos = p.rope_sin = nullptr;
+    auto dq_acc = at::empty({p.B, p.Hq, p.T, D}, fopts);
+    p.dq_acc = dq_acc.data_ptr<float>();
+    check_launch(orion_attn_bwd(plan, p, D, causal, delta.data_ptr<float>(), cur_stream()), "attn_bwd");
+    check_launch(orion_attn_dq_convert(dq_acc.data_ptr<float>(), dq.data_ptr(), dq.stride(0),
+                                       dq.stride(1), dq.stride(2), p.B, p.Hq, p.T, D, cur_stream()),
+                 "attn_dq_convert");
+  }
+  if (plan.bias_in_kernel)
+    check_launch(orion_colsum_partials2(p.bias_part, p.bias_part + prow * ld, bias_grad->data_ptr(),
+                                        (int)prow, (int)ld, is_f32(*bias_grad), cur_stream()),
+                 "attn_bias_colsum");
+  else if (want_bias)
+    attn_bias_colsum_packed(dq, *bias_grad, p.B * p.T, ld);
+  if (!split) unrope();
 }
 
 // ------------------------------------------------------------------ generation (csrc/attn_decode.hip)

@@ -46,6 +46,7 @@
 // and write the result as 16-byte row pieces; fp32 weight gradients store 16 bytes per
 // register quadruple without a swap.
 #include "gemm_common.h"
+#include "lds_once.h"
 
 namespace orion {
 
@@ -892,13 +893,7 @@ static int gemm16_launch(const GemmArgs& a, hipStream_t st) {
   if constexpr (!STAMPS && (EPI == EPI_STORE || EPI == EPI_BIAS || EPI == EPI_BIAS_GELU)) {
     if ((a.flags & 4) && a.slabs) return gemm16_launch<XKM, WKM, EPI, true>(a, st);
   }
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)gemm16_kernel<XKM, WKM, EPI, STAMPS>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, G_LDS) != hipSuccess)
-      return -5;
-    attr = true;
-  }
+  if (dynamic_lds_once<gemm16_kernel<XKM, WKM, EPI, STAMPS>>(G_LDS) != hipSuccess) return -5;
   const long work = (long)((a.M + 255) / 256) * a.tiles_n * a.ksplit;
   if (work <= 0 || work > 0x7FFFFFFFL) return -1;
   // persistent walk (one workgroup per CU) unless a stamped diagnostic or flags & 64 asks for

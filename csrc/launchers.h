@@ -9,7 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "attn_decode_params.h"
-#include "attn_params.h"
+#include "attn_plan.h"
 #include "linear_decode_params.h"
 #include "sample_params.h"
 
@@ -70,16 +70,17 @@ int orion_rope(const void* x, long xsb, long xst, long xsh, void* y, long ysb, l
                const float* cosv, const float* sinv, int B, int T, int H, int D, int pos0, float sign,
                hipStream_t st);
 
-// attention.hip (64-bit addressing; fused backward), attn_fwd.hip, attn_bwd_split.hip
-int orion_attn_fwd(const orion::AttnParams& p, int D, bool causal, hipStream_t st);
-// -2: K / V beyond 32-bit offsets (orion_attn_fwd then runs its own kernel)
-int orion_attn_fwd3(const orion::AttnParams& p, int D, bool causal, hipStream_t st);
-int orion_attn_bwd(const orion::AttnParams& p, int D, bool causal, float* delta, hipStream_t st);
+// attn_fwd.hip, attn_bwd_split.hip, attention.hip (64-bit addressing; fused backward).  What runs is
+// decided by csrc/attn_plan.h; -1: a head dim, or a kernel id, that the file has no kernel for
+int orion_attn_fwd(const orion::AttnParams& p, int D, bool causal, hipStream_t st);  // plans, then launches
+int orion_attn_fwd64(const orion::AttnLaunch& l, const orion::AttnParams& p, int D, bool causal, hipStream_t st);
+// the steps of an orion::attn_bwd_plan of form ATTN_SPLIT / ATTN_FUSED; delta: [B][Hq][T] fp32 scratch
+int orion_attn_bwd_split(const orion::AttnBwdPlan& plan, const orion::AttnParams& p, int D, bool causal,
+                         float* delta, hipStream_t st);
+int orion_attn_bwd(const orion::AttnBwdPlan& plan, const orion::AttnParams& p, int D, bool causal, float* delta,
+                   hipStream_t st);
 int orion_attn_dq_convert(const float* acc, void* dq, long sb, long st_, long sh, int B, int Hq, int T, int D,
                           hipStream_t st);
-// -2: operands beyond 32-bit offsets (the caller takes orion_attn_bwd); -3: p.bias_part given to a form
-// without in-kernel column sums (the caller retries without it)
-int orion_attn_bwd_split(const orion::AttnParams& p, int D, bool causal, float* delta, hipStream_t st);
 
 // gemm.hip, in front of gemm16.hip: -1 shape / leading dims, -2 alignment, -3 an operand the epilogue needs
 int orion_gemm(const void* X, long ldx, const void* W, long ldw, int M, int N, int K, int wkm, int epi, void* out,

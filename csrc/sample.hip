@@ -35,6 +35,7 @@
 
 #include "common.h"
 #include "launchers.h"
+#include "lds_once.h"
 
 namespace orion {
 
@@ -335,13 +336,7 @@ int orion_sample_tokens(const SampleParams& p, hipStream_t st) {
   const long nslots = ((long)p.V + 7 + 7) / 8;  // the most slots a row of V can take (a <= 7)
   if (nslots <= SP_STAGE_SLOTS) {
     constexpr int lds = SP_STAGE_SLOTS * 16;
-    static bool attr = false;
-    if (!attr) {
-      if (hipFuncSetAttribute((const void*)sample_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
-          hipSuccess)
-        return -5;
-      attr = true;
-    }
+    if (dynamic_lds_once<sample_kernel<true>>(lds) != hipSuccess) return -5;
     sample_kernel<true><<<p.B, SP_NT, (size_t)nslots * 16, st>>>(p);
   } else {
     sample_kernel<false><<<p.B, SP_NT, 0, st>>>(p);

@@ -21,6 +21,7 @@
 //     per stage.
 #include "gemm_common.h"
 #include "launchers.h"
+#include "lds_once.h"
 
 namespace orion {
 
@@ -285,13 +286,7 @@ int orion_wgrad(const void* A, long lda, const void* B, long ldb, int M, int N1,
     return gemm16_wgrad(a, bt, st);
   }
   constexpr int lds = WG_NS * WG_KS * 16 * 128 * 4 * (int)sizeof(bf16_t);
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)wgrad_kernel<WG_KS, WG_NS, WG_WM>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-      return -5;
-    attr = true;
-  }
+  if (dynamic_lds_once<wgrad_kernel<WG_KS, WG_NS, WG_WM>>(lds) != hipSuccess) return -5;
   wgrad_kernel<WG_KS, WG_NS, WG_WM><<<ntiles * S, WG_WM * 256, lds, st>>>(
       (const bf16_t*)A, lda, (const bf16_t*)B, ldb, M, N1, N2, t2, ntiles, chunk, S > 1 ? slabs : nullptr,
       out, scale, accumulate, out_f32);

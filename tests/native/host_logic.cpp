@@ -18,7 +18,131 @@ static int failures = 0;
     }                                                                     \
   } while (0)
 
+// ---------------------------------------------------------------- attention plans (csrc/attn_plan.h)
+// The expectations below are written out from the launch tables the kernels were tuned with; they
+// do not call the code under test.
+using orion::AttnLaunch;
+
+static bool is_launch(const AttnLaunch& l, int kernel, int grid, int block, int lds) {
+  return l.kernel == kernel && l.grid == grid && l.block == block && l.lds == lds;
+}
+
+static int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// contiguous (B, T, H, D) views
+static orion::AttnParams attn_shape(int B, int T, int Tk, int Hq, int Hkv, int D) {
+  orion::AttnParams p{};
+  p.B = B, p.T = T, p.Tk = Tk, p.Hq = Hq, p.Hkv = Hkv;
+  p.q_sh = p.k_sh = p.v_sh = p.o_sh = p.do_sh = D;
+  p.q_st = p.o_st = p.do_st = (long)Hq * D;
+  p.k_st = p.v_st = (long)Hkv * D;
+  p.q_sb = p.o_sb = p.do_sb = p.q_st * T;
+  p.k_sb = p.v_sb = p.k_st * Tk;
+  return p;
+}
+
+static void check_fwd_plan(const orion::AttnParams& p, int D, bool causal, const orion::AttnSwitches& s, int qb64,
+                           bool kv_over32) {
+  const AttnLaunch l = orion::attn_fwd_plan(p, D, causal, s, qb64);
+  const int g128 = cdiv(p.T, 128) * p.B * p.Hq, g256 = cdiv(p.T, 256) * p.B * p.Hq, lds = 4 * 64 * D * 2;
+  if (D != 64 && D != 128)
+    CHECK(l.kernel == -1);
+  else if (s.fwd_v2 || kv_over32)
+    CHECK(is_launch(l, orion::ATTN_FWD64, g128, 256, lds));
+  else if (D == 64 && causal && s.fwd_diag)
+    CHECK(is_launch(l, orion::ATTN_FWD3_STAMPED, g256, 256, 32768));
+  else if (D == 64 && causal && !s.fwd_v3)
+    CHECK(is_launch(l, orion::ATTN_FWD4, g128, 256, 32768));
+  else if (D == 64 && qb64 == 2)
+    CHECK(is_launch(l, orion::ATTN_FWD3_QB2, g256, 256, 32768));
+  else
+    CHECK(is_launch(l, orion::ATTN_FWD3_QB1, g128, 256, lds));
+}
+
+static void check_bwd_plan(const orion::AttnParams& p, int D, bool causal, int flags, bool want_bias,
+                           const orion::AttnSwitches& s, bool over32) {
+  const orion::AttnBwdPlan r = orion::attn_bwd_plan(p, D, causal, flags, want_bias, s);
+  if (D != 64 && D != 128) {
+    CHECK(r.form == -1);
+    return;
+  }
+  const int delta_grid = cdiv((long)p.B * p.Hq * p.T * (D / 8), 256);
+  const int kv_grid = cdiv(p.Tk, 128) * p.B * p.Hkv, dq_grid = cdiv(p.T, 128) * p.B * p.Hq;
+  const bool split = ((flags & 4) || !(flags & 8)) && !over32;
+  if (!split) {
+    CHECK(r.form == orion::ATTN_FUSED && !r.bias_in_kernel && r.n == 2);
+    CHECK(is_launch(r.step[0], orion::ATTN_BWD_PRE, delta_grid, 256, 0));
+    CHECK(is_launch(r.step[1], orion::ATTN_BWD, kv_grid, 256, D == 64 ? 78336 : 147968));
+    return;
+  }
+  const bool bias = want_bias && D == 64 && p.T == p.Tk && p.Hq == p.Hkv && p.T % 32 == 0;
+  CHECK(r.form == orion::ATTN_SPLIT && r.bias_in_kernel == bias);
+  const int kv_lds = 2 * 2 * 32 * D * 2 + 4 * 32 * 4 + (D == 128 ? 32 * 4 * D * 2 : 0), dq_lds = 4 * 64 * D * 2;
+  CHECK(kv_lds == (D == 64 ? 16896 : 66048));
+  if (D == 64 && s.bwd_diag) {
+    CHECK(r.n == 2 && is_launch(r.step[0], orion::ATTN_DELTA, delta_grid, 256, 0) &&
+          is_launch(r.step[1], orion::ATTN_KV_STAMPED, kv_grid, 256, kv_lds));
+  } else if (D == 64 && !s.dq_v3) {
+    CHECK(r.n == 2 && is_launch(r.step[0], bias ? orion::ATTN_DQ4_BIAS : orion::ATTN_DQ4, dq_grid, 256, 32768) &&
+          is_launch(r.step[1], orion::ATTN_KV, kv_grid, 256, kv_lds));
+  } else if (D == 128 && !s.delta_pass) {
+    CHECK(r.n == 2 && is_launch(r.step[0], orion::ATTN_DQ_FD, dq_grid, 256, dq_lds) &&
+          is_launch(r.step[1], orion::ATTN_KV, kv_grid, 256, kv_lds));
+  } else {
+    CHECK(r.n == 3 && is_launch(r.step[0], bias ? orion::ATTN_DELTA_BIAS : orion::ATTN_DELTA, delta_grid, 256, 0) &&
+          is_launch(r.step[1], orion::ATTN_KV, kv_grid, 256, kv_lds) &&
+          is_launch(r.step[2], bias ? orion::ATTN_DQ_BIAS : orion::ATTN_DQ, dq_grid, 256, dq_lds));
+  }
+}
+
+static void check_attention_plans() {
+  // the switches: the documented values, read once
+  setenv("ORION_ATTN_FWD", "v3", 1);
+  setenv("ORION_ATTN_DQ", "v3", 1);
+  setenv("ORION_ATTN_DELTA", "pass", 1);
+  setenv("ORION_ATTN_DIAG", "0", 1);
+  unsetenv("ORION_ATTN_FWD_DIAG");
+  const orion::AttnSwitches env = orion::attn_switches();
+  CHECK(!env.fwd_v2 && env.fwd_v3 && env.dq_v3 && env.delta_pass && !env.fwd_diag && !env.bwd_diag);
+  setenv("ORION_ATTN_FWD", "v2", 1);
+  CHECK(!orion::attn_switches().fwd_v2);  // not read again
+
+  for (int sw = 0; sw < 64; ++sw) {
+    const orion::AttnSwitches s{bool(sw & 1), bool(sw & 2), bool(sw & 4), bool(sw & 8), bool(sw & 16), bool(sw & 32)};
+    for (int D : {64, 128, 96})
+      for (bool causal : {false, true}) {
+        for (int Hkv : {4, 2})          // MHA, GQA
+          for (int T : {160, 300})      // T % 32 == 0 and not; 2 and 3 tiles of 128
+            for (int Tk : {T, T + 100}) {
+              const orion::AttnParams p = attn_shape(2, T, Tk, 4, Hkv, D);
+              for (int qb64 : {1, 2}) check_fwd_plan(p, D, causal, s, qb64, false);
+              for (int flags : {0, 4, 8})
+                for (bool want_bias : {false, true}) check_bwd_plan(p, D, causal, flags, want_bias, s, false);
+            }
+        // operands just below and at the 2^31-byte limit of the 32-bit offsets: 65 tokens whose last row
+        // starts 64 strides in, so ((T - 1) * stride + (Hq - 1) * D + D) * 2 == 2^31 at the strides below
+        if (D == 96) continue;
+        const long kv_at = ((1L << 30) - D) / 64, q_at = ((1L << 30) - 4 * D) / 64;
+        for (int which = 0; which < 4; ++which)
+          for (int below : {1, 0}) {
+            orion::AttnParams p = attn_shape(2, 65, 65, 4, 2, D);
+            (which == 0 ? p.k_st : which == 1 ? p.v_st : which == 2 ? p.q_st : p.do_st) =
+                (which < 2 ? kv_at : q_at) - below;
+            check_fwd_plan(p, D, causal, s, 2, which < 2 && !below);
+            for (int flags : {0, 4, 8}) check_bwd_plan(p, D, causal, flags, true, s, !below);
+          }
+      }
+  }
+  // the (D, causal) -> template argument helper
+  for (int D : {64, 128, 96})
+    for (bool causal : {false, true}) {
+      const int r = orion::attn_dispatch(D, causal, [](auto d, auto c) { return d() * 2 + (c() ? 1 : 0); });
+      CHECK(r == (D == 96 ? -1 : D * 2 + (causal ? 1 : 0)));
+    }
+}
+
 int main() {
+  check_attention_plans();
   // split-K planning over the shapes the models produce (and odd ones)
   const int Ms[] = {32, 96, 256, 4096, 8192, 8224, 16384, 65536, 131072, 262144};
   const int Ns[] = {8, 64, 264, 768, 1000, 2304, 3072, 4096, 11008, 50304};

@@ -243,6 +243,50 @@ def test_forward_kernel_variants_match_reference(env):
     assert all("bad rows 0 /" in ln for ln in lines), r.stdout
 
 
+VARIANT_SWITCHES = {"ORION_ATTN_FWD": "v3", "ORION_ATTN_DQ": "v3", "ORION_ATTN_DELTA": "pass"}
+
+
+def _variant_switch_cases():
+    """Forward and backward through the kernels the switches select.  T = 160: two 128-row query
+    tiles and three 64-key tiles, the last of each partial."""
+    for D in (64, 128):
+        for causal in (True, False):
+            q, k, v, do = _inputs(2, 160, 160, 4, 2, D)
+            _check(_run(q, k, v, do, causal, 0), _ref(q, k, v, do, causal), _sdpa_bf16(q, k, v, do, causal))
+    # packed QKV with the bias output (MHA, D = 64, T % 32 == 0: column sums inside the kernels)
+    B, T, H, D, causal = 2, 160, 2, 64, True
+    g = torch.Generator(device=DEV).manual_seed(5)
+    qkv = torch.randn(B, T, 3 * H, D, device=DEV, dtype=torch.bfloat16, generator=g)
+    do = torch.randn(B, T, H, D, device=DEV, dtype=torch.bfloat16, generator=g)
+    q, k, v = qkv[:, :, :H], qkv[:, :, H:2 * H], qkv[:, :, 2 * H:]
+    scale = 1.0 / math.sqrt(D)
+    o, lse = _C().attn_fwd(q, k, v, causal, scale)
+    d = torch.empty_like(qkv)
+    db = torch.full((3 * H * D,), float("nan"), device=DEV, dtype=torch.float32)
+    _C().attn_bwd(do, q, k, v, o, lse, causal, scale, d[:, :, :H], d[:, :, H:2 * H], d[:, :, 2 * H:], 0, db)
+    want, base = _ref(q, k, v, do, causal), _sdpa_bf16(q, k, v, do, causal)
+    _check((o, d[:, :, :H], d[:, :, H:2 * H], d[:, :, 2 * H:]), want, base)
+    colsum = lambda grads: torch.cat(list(grads), dim=2).reshape(B * T, -1).float().sum(0)
+    within_bf16_budget("db", db, colsum(want[1:]), colsum(base[1:]))
+    torch.cuda.synchronize()
+    print("variant switches ok")
+
+
+def test_variant_switches_match_reference():
+    """ORION_ATTN_FWD=v3, ORION_ATTN_DQ=v3 and ORION_ATTN_DELTA=pass (the forms the defaults replaced)
+    against the fp32 reference.  The switches are read once per process, so the cases run in a child
+    process: this module as a script."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {**os.environ, **VARIANT_SWITCHES,
+           "PYTHONPATH": os.pathsep.join(p for p in (root, os.environ.get("PYTHONPATH")) if p)}
+    r = subprocess.run([sys.executable, os.path.abspath(__file__)], env=env, capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0 and "variant switches ok" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
+
+
 @pytest.mark.parametrize("form", [0, SPLIT, FUSED])
 @pytest.mark.parametrize("D,Hq,Hkv,T", [(64, 4, 4, 256), (64, 4, 4, 200), (64, 4, 2, 256), (128, 4, 2, 256)])
 @pytest.mark.parametrize("causal", [True, False])
@@ -336,3 +380,7 @@ def test_fused_qkv_rope_attention_node(B, T, Hq, Hkv, pos0, monkeypatch):
     o.backward(do.float())
     for name, a, b, cc in zip(("o", "dx", "dw"), got, (o.detach(), xr.grad, wr.grad), base):
         within_bf16_budget(name, a, b, cc)
+
+
+if __name__ == "__main__":  # the child process of test_variant_switches_match_reference
+    _variant_switch_cases()
