@@ -20,6 +20,9 @@ import torch.nn.functional as F
 
 from . import reference as ref
 from ._ext import ext_available, load_ext
+# loaded here, before ``def linear`` below binds the name: the first import of a submodule
+# sets it as an attribute of the package, which later would replace the function
+from .linear import linear_hip
 
 _BACKEND = os.environ.get("ORION_AMD_OPS", "hip")
 
@@ -125,7 +128,6 @@ def linear(x, weight, bias=None):
     """x W^T + b (hipBLASLt GEMM; bias gradient by the HIP column-sum kernel)."""
     b = _gpu(x)
     if b == "hip":
-        from .layernorm import linear_hip
         return linear_hip(x, weight, bias)
     return F.linear(x, weight.to(x.dtype), None if bias is None else bias.to(x.dtype))
 
@@ -133,7 +135,7 @@ def linear(x, weight, bias=None):
 def rms_norm(x, weight, eps=1e-5):
     b = _gpu(x)
     if b == "hip":
-        from .rmsnorm import rms_norm_hip
+        from .layernorm import rms_norm_hip
         return rms_norm_hip(x, weight, eps)
     if b == "torch":
         xf = x.float()
@@ -300,7 +302,6 @@ def linear_attention_qkv(x, weight, bias, n_head, causal=True):
     into the split kernels) instead of a column-sum pass over the packed dQKV."""
     if _gpu(x) == "hip" and bias is not None:
         from .flash_attn import flash_attention_qkv
-        from .layernorm import linear_hip
         qkv = linear_hip(x, weight, bias.detach())
         return flash_attention_qkv(qkv, n_head, causal, bias)
     return attention_qkv(linear(x, weight, bias), n_head, causal)

@@ -9,9 +9,9 @@ import os
 import torch
 
 from ._ext import C
-from .gemm import EPI_BIAS_GELU, linear_dgrad, linear_fwd, wgrad, wgrad_into
-from .grad_sink import sink_of
-from .layernorm import _claim, _notify, _unless, _view
+from .gemm import (EPI_BIAS_GELU, bf16_dense_aligned, bias_grad, gemm16_addressable, linear_dgrad,
+                   linear_fwd, weight_grad)
+from .grad_sink import claim_bf16, finish, out_view, sink_of
 
 
 class _BiasGelu(torch.autograd.Function):
@@ -27,11 +27,10 @@ class _BiasGelu(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, bb = ctx.saved_tensors
-        (sb,) = _claim((ctx.bias,))
-        dx, db = C().bias_gelu_bwd(dy.contiguous(), x, bb, _view(sb))
-        _notify(sb)
-        db = _unless(db, sb)
-        return dx.view(x.shape), (None if db is None else db.to(ctx.b_dtype))
+        (sb,) = claim_bf16(ctx.bias)
+        dx, db = C().bias_gelu_bwd(dy.contiguous(), x, bb, out_view(sb))
+        db = finish(db, sb, ctx.b_dtype)
+        return dx.view(x.shape), db
 
 
 def bias_gelu_hip(x, bias):
@@ -69,11 +68,8 @@ _FUSED_MLP = os.environ.get("ORION_FUSED_MLP", "1") != "0"
 def fused_mlp_ok(a, weight) -> bool:
     """The fused tail needs bf16 operands the in-tree GEMM takes: a (..., F) contiguous,
     weight (C, F) contiguous with C % 64 == 0 (the reduction dim of the input gradient)."""
-    from .gemm import gemm16_addressable
-    return (_FUSED_MLP and a.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16
-            and a.is_contiguous() and weight.is_contiguous() and weight.shape[0] % 64 == 0
-            and weight.shape[1] % 8 == 0 and a.data_ptr() % 16 == 0
-            and weight.data_ptr() % 16 == 0
+    return (_FUSED_MLP and bf16_dense_aligned(a, weight) and weight.shape[0] % 64 == 0
+            and weight.shape[1] % 8 == 0
             and gemm16_addressable(weight.shape[0], weight.shape[0], weight.shape[1], True)
             and gemm16_addressable(weight.shape[1], weight.shape[1], weight.shape[0], False))
 
@@ -101,27 +97,12 @@ class _GeluLinear(torch.autograd.Function):
         F_ = a.shape[-1]
         dy2 = dy.reshape(-1, dy.shape[-1])
         h2 = h.reshape(-1, F_)
-        sfc, sb = _claim((ctx.fc_bias, ctx.bias))
-        da, dbfc = C().gemm_gelu_bwd(dy2, w, a.reshape(-1, F_), bb, _view(sfc))
-        _notify(sfc)
-        dbfc = None if ctx.fc_bias is None else _unless(dbfc, sfc)
-        dw = db = None
-        if ctx.needs_input_grad[2]:
-            if ctx.sink is not None:
-                wgrad_into(dy2, h2, ctx.sink.view, ctx.sink.take())
-                ctx.sink.notify()
-            else:
-                dw = wgrad(dy2, h2)
-        if ctx.bias is not None and ctx.needs_input_grad[3]:
-            db = C().colsum(dy2.contiguous(), _view(sb))
-            if sb is not None:
-                db = None
-            _notify(sb)
-        if dbfc is not None:
-            dbfc = dbfc.to(ctx.fc_bias.dtype)
-        if db is not None:
-            db = db.to(ctx.bias.dtype)
-        return da.view(a.shape), dbfc, dw, db
+        (sfc,) = claim_bf16(ctx.fc_bias)
+        da, dbfc = C().gemm_gelu_bwd(dy2, w, a.reshape(-1, F_), bb, out_view(sfc))
+        dbfc = finish(None if ctx.fc_bias is None else dbfc, sfc)  # cast after the GEMMs
+        dw = weight_grad(dy2, h2, ctx.sink) if ctx.needs_input_grad[2] else None
+        db = bias_grad(dy2, ctx.bias) if ctx.bias is not None and ctx.needs_input_grad[3] else None
+        return da.view(a.shape), (None if dbfc is None else dbfc.to(ctx.fc_bias.dtype)), dw, db
 
 
 def gelu_linear_hip(a, b_fc, weight, bias=None):
@@ -131,11 +112,8 @@ def gelu_linear_hip(a, b_fc, weight, bias=None):
 # ORION_FUSED_MLP=1 (see _FusedMLP): the GPT-2 MLP with both GELU passes inside GEMM epilogues
 def mlp_ok(x, w_fc, w_proj) -> bool:
     C_ = x.shape[-1]
-    return (_FUSED_MLP and x.dtype == torch.bfloat16 and w_fc.dtype == torch.bfloat16
-            and w_proj.dtype == torch.bfloat16 and x.is_contiguous() and w_fc.is_contiguous()
-            and w_proj.is_contiguous() and C_ % 64 == 0 and w_fc.shape[0] % 64 == 0
-            and w_fc.shape[0] % 8 == 0 and w_proj.shape[0] % 8 == 0
-            and x.data_ptr() % 16 == 0 and w_fc.data_ptr() % 16 == 0 and w_proj.data_ptr() % 16 == 0)
+    return (_FUSED_MLP and bf16_dense_aligned(x, w_fc, w_proj) and C_ % 64 == 0
+            and w_fc.shape[0] % 64 == 0 and w_fc.shape[0] % 8 == 0 and w_proj.shape[0] % 8 == 0)
 
 
 class _FusedMLP(torch.autograd.Function):
@@ -195,24 +173,17 @@ def mlp_backward(dy2, x2, a, h, w_fc, w_proj, biases, sinks, deriv, needs, proj_
     b_fc, w_proj, b_proj); without ``proj_bias_grad`` the caller owns db_proj."""
     b_fc, b_proj = biases
     s_fc, s_proj = sinks
-    sbfc, sbproj = _claim((b_fc, b_proj if proj_bias_grad else None))
+    (sbfc,) = claim_bf16(b_fc)
     # a already holds the fc bias: GELU'(a), no bias operand (or a IS the derivative)
-    da, dbfc = C().gemm_gelu_bwd(dy2, w_proj, a, None, _view(sbfc), deriv)
-    _notify(sbfc)
-    dbfc = None if b_fc is None else _unless(dbfc, sbfc)
+    da, dbfc = C().gemm_gelu_bwd(dy2, w_proj, a, None, out_view(sbfc), deriv)
+    dbfc = finish(None if b_fc is None else dbfc, sbfc)  # cast after the GEMMs
     grads = [None, None, None, None, None]
 
     def proj_grads():
         if needs[3]:
-            if s_proj is not None:
-                wgrad_into(dy2, h, s_proj.view, s_proj.take())
-                s_proj.notify()
-            else:
-                grads[3] = wgrad(dy2, h)
+            grads[3] = weight_grad(dy2, h, s_proj)
         if proj_bias_grad and b_proj is not None and needs[4]:
-            db = C().colsum(dy2, _view(sbproj))
-            grads[4] = None if sbproj is not None else db.to(b_proj.dtype)
-            _notify(sbproj)
+            grads[4] = bias_grad(dy2, b_proj)
 
     def fc_dgrad():
         if needs[0]:
@@ -220,17 +191,21 @@ def mlp_backward(dy2, x2, a, h, w_fc, w_proj, biases, sinks, deriv, needs, proj_
 
     def fc_wgrad():
         if needs[1]:
-            if s_fc is not None:
-                wgrad_into(da, x2, s_fc.view, s_fc.take())
-                s_fc.notify()
-            else:
-                grads[1] = wgrad(da, x2)
-    for step in {"0": (proj_grads, fc_dgrad, fc_wgrad), "1": (fc_dgrad, fc_wgrad, proj_grads),
-                 "2": (fc_wgrad, fc_dgrad, proj_grads)}[_MLP_BWD_ORDER]:
-        step()
+            grads[1] = weight_grad(da, x2, s_fc)
+    _run_in_order(_MLP_BWD_ORDER, proj_grads, fc_dgrad, fc_wgrad)
     if dbfc is not None:
         grads[2] = dbfc.to(b_fc.dtype)
     return grads
+
+
+def _run_in_order(order, out_grads, in_dgrad, in_wgrad):
+    """The three steps of a two-GEMM feed-forward's backward after its fused first GEMM, in the
+    order named by _MLP_BWD_ORDER / _SWIGLU_BWD_ORDER (below): the output projection's
+    gradients, then the input projection's input and weight gradients (0); the output
+    projection's last (1); as 1 with the weight gradient before the input gradient (2)."""
+    for step in {"0": (out_grads, in_dgrad, in_wgrad), "1": (in_dgrad, in_wgrad, out_grads),
+                 "2": (in_wgrad, in_dgrad, out_grads)}[order]:
+        step()
 
 
 # ORION_GELU_DERIV=1 (default, round 5): the fused MLP's forward epilogue stores GELU'(a) in
@@ -272,14 +247,10 @@ _SWIGLU_FWD = os.environ.get("ORION_SWIGLU_FWD", "gemm")
 
 
 def swiglu_mlp_ok(x, w_gu, w_down) -> bool:
-    from .gemm import gemm16_addressable
     C_, F2 = x.shape[-1], w_gu.shape[0]
     F_ = F2 // 2
-    return (_FUSED_SWIGLU and x.dtype == torch.bfloat16 and w_gu.dtype == torch.bfloat16
-            and w_down.dtype == torch.bfloat16 and x.is_contiguous() and w_gu.is_contiguous()
-            and w_down.is_contiguous() and F2 % 2 == 0 and w_down.shape == (C_, F_)
-            and C_ % 64 == 0 and F_ % 8 == 0 and x.data_ptr() % 16 == 0
-            and w_gu.data_ptr() % 16 == 0 and w_down.data_ptr() % 16 == 0
+    return (_FUSED_SWIGLU and bf16_dense_aligned(x, w_gu, w_down) and F2 % 2 == 0
+            and w_down.shape == (C_, F_) and C_ % 64 == 0 and F_ % 8 == 0
             and gemm16_addressable(C_, C_, F_, True) and gemm16_addressable(2 * F_, 2 * F_, F_, False))
 
 
@@ -332,11 +303,7 @@ def swiglu_backward(dy2, x2, gu, h, w_gu, w_down, sinks, needs):
 
     def down_wgrad():
         if needs[2]:
-            if s_down is not None:
-                wgrad_into(dy2, h, s_down.view, s_down.take())
-                s_down.notify()
-            else:
-                grads[2] = wgrad(dy2, h)
+            grads[2] = weight_grad(dy2, h, s_down)
 
     def gu_dgrad():
         if needs[0]:
@@ -344,15 +311,8 @@ def swiglu_backward(dy2, x2, gu, h, w_gu, w_down, sinks, needs):
 
     def gu_wgrad():
         if needs[1]:
-            if s_gu is not None:
-                wgrad_into(dgu, x2, s_gu.view, s_gu.take())
-                s_gu.notify()
-            else:
-                grads[1] = wgrad(dgu, x2)
-    # the same orders as _FusedMLP (_SWIGLU_BWD_ORDER)
-    for step in {"0": (down_wgrad, gu_dgrad, gu_wgrad), "1": (gu_dgrad, gu_wgrad, down_wgrad),
-                 "2": (gu_wgrad, gu_dgrad, down_wgrad)}[_SWIGLU_BWD_ORDER]:
-        step()
+            grads[1] = weight_grad(dgu, x2, s_gu)
+    _run_in_order(_SWIGLU_BWD_ORDER, down_wgrad, gu_dgrad, gu_wgrad)
     return grads
 
 

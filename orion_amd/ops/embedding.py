@@ -27,8 +27,8 @@ import torch
 
 from ._ext import C
 from .determinism import deterministic
-from .grad_sink import sink_of
-from .layernorm import _bf16, _claim, _grad, _notify, _unless, _view
+from .grad_sink import claim_bf16, sink_of
+from .layernorm import as_bf16, layer_norm_backward
 
 _CHECK_ALWAYS = os.environ.get("ORION_CHECK_IDS") == "1"
 _checked: set = set()
@@ -50,42 +50,55 @@ def id_error(device=None) -> bool:
     return bool(C().embed_id_error(dev.index if dev.index is not None else 0))
 
 
-def _dense_table_grad(dx2, idx, V):
-    return torch.ops.aten.embedding_dense_backward(dx2, idx.reshape(-1), V, -1, False)
+def _table_grad(dx2, idx, wte):
+    """The token table's gradient from the (tokens, C) gradient of the gathered rows, as the
+    table's LAST use of the backward (ops/grad_sink.py).  fp32 arena: scatter-added into the
+    slice with fp32 atomics; bf16 arena or deterministic mode: the sort-based dense backward,
+    added (or copied) into the slice; no arena: the dense backward, returned."""
+    V, Cc = wte.shape
+    st = sink_of(wte)
+    if st is not None and st.view.dtype == torch.float32 and not deterministic():
+        view, acc = st.last_use_target()
+        if not acc:  # first producer of the step: the slice is not pre-zeroed
+            view.zero_()
+        C().embed_scatter_add_(dx2, idx, view.view(-1, Cc))
+        st.notify(last=True)
+        return None
+    g = torch.ops.aten.embedding_dense_backward(dx2, idx.reshape(-1), V, -1, False)
+    if st is None:
+        return g.to(wte.dtype)
+    view, acc = st.last_use_target()
+    if acc:
+        view.view(-1, Cc).add_(g)
+    else:
+        view.view(-1, Cc).copy_(g)
+    st.notify(last=True)
+    return None
 
 
 class _EmbedLayerNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, idx, wte, wpe, w, b, eps):
-        s, y, mean, rstd = C().embed_layernorm_fwd(idx, _bf16(wte), _bf16(wpe), _bf16(w), _bf16(b),
-                                                   float(eps))
+        s, y, mean, rstd = C().embed_layernorm_fwd(idx, as_bf16(wte), as_bf16(wpe), as_bf16(w),
+                                                   as_bf16(b), float(eps))
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(idx, s, w, mean, rstd)
-        ctx.has_bias = b is not None
-        ctx.b_dtype = None if b is None else b.dtype
         ctx.params = (w, b)
         ctx.tables = (wte, wpe)
         return s, y
 
     @staticmethod
     def backward(ctx, ds, dy):
-        idx, s, w, mean, rstd = ctx.saved_tensors
+        idx, s, _, mean, rstd = ctx.saved_tensors
         wte, wpe = ctx.tables
         B, T, Cc = s.shape
-        if dy is None:
-            dy = torch.zeros_like(s)
-        dres = None if ds is None else ds.contiguous()
-        sw, sb = _claim(ctx.params)
-        dx, dw, db, _ = C().layernorm_bwd(dy.contiguous(), s, _bf16(w), mean, rstd, ctx.has_bias,
-                                          dres, False, _view(sw), _view(sb))
-        _notify(sw, sb)
-        dw, db = _unless(dw, sw), _unless(db, sb)
+        dx, dw, db, _ = layer_norm_backward(dy, s, mean, rstd, *ctx.params, dres=ds)
         dx2 = dx.view(B * T, Cc)
 
         # position table: column sums of dx over the batch into rows 0..T-1
         dwpe = None
         if ctx.needs_input_grad[2]:
-            (spe,) = _claim((wpe,))
+            (spe,) = claim_bf16(wpe)
             if spe is not None:
                 view = spe.view.view(-1, Cc)
                 C().batch_sum_(dx.view(B, T * Cc), view[:T].reshape(-1))
@@ -98,27 +111,8 @@ class _EmbedLayerNorm(torch.autograd.Function):
                 dwpe = dwpe.to(wpe.dtype)
 
         # token table (tied to the LM head)
-        dwte = None
-        if ctx.needs_input_grad[1]:
-            st = sink_of(wte)
-            if st is not None and st.view.dtype == torch.float32 and not deterministic():
-                view, acc = st.last_use_target()
-                if not acc:  # first producer of the step: the slice is not pre-zeroed
-                    view.zero_()
-                C().embed_scatter_add_(dx2, idx, view.view(-1, Cc))
-                st.notify(last=True)
-            elif st is not None:
-                g = _dense_table_grad(dx2, idx, wte.shape[0])
-                view, acc = st.last_use_target()
-                if acc:
-                    view.view(-1, Cc).add_(g)
-                else:
-                    view.view(-1, Cc).copy_(g)
-                st.notify(last=True)
-            else:
-                dwte = _dense_table_grad(dx2, idx, wte.shape[0]).to(wte.dtype)
-        return (None, dwte, dwpe, _grad(dw, w.dtype),
-                (_grad(db, ctx.b_dtype) if ctx.has_bias else None), None)
+        dwte = _table_grad(dx2, idx, wte) if ctx.needs_input_grad[1] else None
+        return None, dwte, dwpe, dw, db, None
 
 
 def embed_layer_norm_hip(idx, wte, wpe, weight, bias, eps=1e-5):
@@ -146,28 +140,7 @@ class _Embedding(torch.autograd.Function):
         wte = ctx.table
         if not ctx.needs_input_grad[1]:
             return None, None
-        Cc = wte.shape[1]
-        dy2 = dy.reshape(-1, Cc)
-        if dy2.dtype != torch.bfloat16:
-            dy2 = dy2.to(torch.bfloat16)
-        st = sink_of(wte)
-        if st is not None and st.view.dtype == torch.float32 and not deterministic():
-            view, acc = st.last_use_target()
-            if not acc:  # first producer of the step: the slice is not pre-zeroed
-                view.zero_()
-            C().embed_scatter_add_(dy2, idx, view.view(-1, Cc))
-            st.notify(last=True)
-            return None, None
-        if st is not None:
-            g = _dense_table_grad(dy2, idx, wte.shape[0])
-            view, acc = st.last_use_target()
-            if acc:
-                view.view(-1, Cc).add_(g)
-            else:
-                view.view(-1, Cc).copy_(g)
-            st.notify(last=True)
-            return None, None
-        return None, _dense_table_grad(dy2, idx, wte.shape[0]).to(wte.dtype)
+        return None, _table_grad(as_bf16(dy.reshape(-1, wte.shape[1])), idx, wte)
 
 
 def embedding_hip(idx, weight):

@@ -15,7 +15,9 @@ import torch
 
 from ._ext import C
 from .determinism import deterministic
-from .grad_sink import sink_of
+from .gemm import bf16_dense_aligned, gemm16_addressable
+from .grad_sink import claim_bf16, finish, out_view, sink_of
+from .linear import linear_input_weight_grads
 
 
 def _bwd_flags() -> int:
@@ -56,17 +58,11 @@ class _FlashQKV(torch.autograd.Function):
         want_db = bias is not None and ctx.needs_input_grad[3]
         sb = db = None
         if want_db:
-            from .grad_sink import claim
-            sb = claim(bias) if bias.dtype == torch.bfloat16 else None
-            db = sb.view if sb is not None else torch.empty(C3, dtype=qkv.dtype, device=qkv.device)
+            (sb,) = claim_bf16(bias)
+            db = out_view(sb) if sb is not None else torch.empty(C3, dtype=qkv.dtype, device=qkv.device)
         C().attn_bwd(do4, v5[:, :, 0], v5[:, :, 1], v5[:, :, 2], o, lse, causal, scale,
                      d5[:, :, 0], d5[:, :, 1], d5[:, :, 2], _bwd_flags(), db)
-        if sb is not None:  # written into the arena slice; never handed back to autograd
-            sb.notify()
-            db = None
-        elif db is not None:
-            db = db.to(bias.dtype)
-        return dqkv, None, None, db
+        return dqkv, None, None, (finish(db, sb, bias.dtype) if want_db else None)
 
 
 def flash_attention_qkv(qkv, n_head, causal=True, qkv_bias=None):
@@ -140,7 +136,7 @@ class _QKVRopeFlash(torch.autograd.Function):
     so the separate rope pass (a read and a write of the q | k heads) is gone; the attention
     reads the three head ranges of that buffer.  Backward: as _RopeFlashPacked, the attention
     kernels write dq / dk un-rotated into one packed dqkv, which then feeds the projection's
-    input and weight gradients (ops/layernorm.py linear_input_weight_grads)."""
+    input and weight gradients (ops/linear.py linear_input_weight_grads)."""
 
     @staticmethod
     def forward(ctx, x, w, n_q, n_kv, cos, sin, pos0):
@@ -157,7 +153,6 @@ class _QKVRopeFlash(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, do):
-        from .layernorm import linear_input_weight_grads
         x, w, qkv, o, lse, cos, sin = ctx.saved_tensors
         n_q, n_kv, pos0, scale = ctx.meta
         dqkv = torch.empty_like(qkv)
@@ -174,12 +169,10 @@ _QKV_ROPE = os.environ.get("ORION_QKV_ROPE", "1") != "0"
 
 
 def qkv_rope_eligible(x, w, n_q, n_kv, cos) -> bool:
-    from .gemm import gemm16_addressable
     H3 = n_q + 2 * n_kv
-    if not (_QKV_ROPE and x.is_cuda and x.dim() == 3 and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
+    if not (_QKV_ROPE and x.is_cuda and x.dim() == 3 and bf16_dense_aligned(x, w)
             and w.dim() == 2 and w.shape[0] % H3 == 0 and w.shape[0] // H3 == 128 and x.stride(-1) == 1
-            and x.is_contiguous() and w.is_contiguous() and x.shape[-1] % 64 == 0 and x.data_ptr() % 16 == 0
-            and w.data_ptr() % 16 == 0 and cos.dtype == torch.float32 and cos.is_contiguous()):
+            and x.shape[-1] % 64 == 0 and cos.dtype == torch.float32 and cos.is_contiguous()):
         return False
     return gemm16_addressable(x.shape[-1], x.shape[-1], w.shape[0], False)
 

@@ -24,6 +24,7 @@ import torch
 
 from ._ext import C
 from .determinism import deterministic
+from .grad_sink import claim_bf16, finish, out_view
 
 # ------------------------------------------------------------------ forward / dgrad GEMMs
 # Linear-layer forward (x W^T [+ b]) and input gradient (dy W).  ORION_GEMM=auto (default):
@@ -80,6 +81,13 @@ def gemm16_addressable(ldx: int, K: int, N: int, w_kmajor: bool) -> bool:
     bands = 256 * 2 * max(ldx, N, 1)
     wb = K * N * 2 if w_kmajor else 256 * 2 * K
     return bands < _OFF_LIMIT and wb < _OFF_LIMIT
+
+
+def bf16_dense_aligned(*tensors) -> bool:
+    """Every tensor bf16, contiguous and based at a 16-byte boundary: what the fused nodes'
+    eligibility tests ask of their operands before the shape conditions."""
+    return all(t.dtype == torch.bfloat16 and t.is_contiguous() and t.data_ptr() % 16 == 0
+               for t in tensors)
 
 
 def _hip_eligible(x: torch.Tensor, w: torch.Tensor, w_kmajor: bool) -> bool:
@@ -276,3 +284,21 @@ def wgrad(dy: torch.Tensor, x: torch.Tensor, scale: torch.Tensor | None = None) 
     slabs = torch.bmm(dy.contiguous().view(S, M // S, n1).transpose(1, 2),
                       x.contiguous().view(S, M // S, n2), out_dtype=torch.float32)
     return C().slab_sum(slabs, scale)
+
+
+def weight_grad(dy2, x2, sink, scale=None):
+    """dW = dy2^T x2 [* scale] of a linear layer: written straight into the gradient arena
+    through ``sink`` when there is one (overwriting on the step's first write, accumulating
+    after; the sink is notified and None returned), else returned for ``AccumulateGrad``."""
+    if sink is None:
+        return wgrad(dy2, x2, scale)
+    wgrad_into(dy2, x2, sink.view, sink.take(), scale)
+    sink.notify()
+    return None
+
+
+def bias_grad(dy2, bias):
+    """db = colsum(dy2) by the deterministic two-stage column-sum kernel, into ``bias``'s arena
+    slice when it can be claimed (then None is returned), else returned in the bias's dtype."""
+    (sb,) = claim_bf16(bias)
+    return finish(C().colsum(dy2.contiguous(), out_view(sb)), sb, bias.dtype)

@@ -7,8 +7,9 @@ re-reads the new gradient and the arena slice and writes the slice back (for
 Llama-7B at 16k tokens per micro-batch: ~20 ms per step, ~2.4 % of it).
 
 Instead, the arena attaches a :class:`GradSink` to each parameter it owns, and the
-GEMM-backed backward functions (``ops.layernorm._Linear``, the fused LM head in
-``ops.xent``) write ``dW`` straight into the arena slice -- overwriting it on the first
+GEMM-backed backward functions (``ops.linear._Linear``, the fused MLPs, the fused LM head in
+``ops.xent``: all through ``ops.gemm.weight_grad``) write ``dW`` straight into the arena
+slice -- overwriting it on the first
 write of a step, accumulating in the GEMM epilogue afterwards (gradient accumulation
 over micro-batches) -- and return ``None`` for the weight.  Because no
 ``AccumulateGrad`` runs, the sink then notifies the arena's gradient listeners (the
@@ -28,6 +29,12 @@ embedding's writes -- and, since ``AccumulateGrad`` runs no hook for an undefine
 gradient, the all-sink case is reported during the backward rather than only at
 ``finish()``.
 ``ORION_DIRECT_GRADS=0`` disables the mechanism.
+
+Small gradients (norm weights, biases) are reductions whose kernel takes the slice as its
+output.  Their producers follow one protocol, the three functions at the end of this file:
+``claim_bf16`` the parameters' sinks, pass ``out_view(sink)`` to the kernel, and hand each
+returned gradient through ``finish``, which notifies the sink and keeps a gradient written
+through it from also reaching ``AccumulateGrad``.
 """
 from __future__ import annotations
 
@@ -138,3 +145,25 @@ def claim(param: torch.Tensor | None) -> GradSink | None:
         return None
     sk.fresh = False
     return sk
+
+
+def claim_bf16(*params: torch.Tensor | None) -> tuple:
+    """``claim`` for each of ``params``: one sink or None per parameter.  Only bf16 parameters
+    are claimed (the reduction kernels' outputs are bf16 or the fp32 arena of a bf16 model)."""
+    return tuple(claim(p) if p is not None and p.dtype == torch.bfloat16 else None for p in params)
+
+
+def out_view(sink: GradSink | None) -> torch.Tensor | None:
+    """What to pass as the kernel's gradient output: the claimed slice, or None (allocate)."""
+    return None if sink is None else sink.view
+
+
+def finish(grad: torch.Tensor | None, sink: GradSink | None, dtype: torch.dtype | None = None):
+    """After the kernel that produced ``grad``: what the autograd node returns for it.  With a
+    sink the gradient is in the arena: the sink is notified and None returned, never the slice
+    (``p.grad += p.grad`` would double it).  Without one ``grad`` is returned, cast to ``dtype``
+    if given (None stays None)."""
+    if sink is not None:
+        sink.notify()
+        return None
+    return grad if grad is None or dtype is None else grad.to(dtype)

@@ -32,7 +32,8 @@ from .activations import (mlp_backward, mlp_fc_forward, mlp_ok, swiglu_backward,
                           swiglu_mlp_ok)
 from .determinism import deterministic
 from .grad_sink import sink_of
-from .layernorm import _bf16, _claim, _grad, _notify, _unless, _view, linear_input_weight_grads
+from .layernorm import as_bf16, layer_norm_backward, rms_norm_backward
+from .linear import linear_input_weight_grads
 
 # ORION_RESID_GEMM=0: the projection as a plain GEMM + the fused add + LayerNorm kernel (A/B);
 # =attn: only the attention site
@@ -71,27 +72,19 @@ def _residual_gemm(inp2, w, rb, x2):
 
 
 def _ln_forward(ctx, s2, ln_w, ln_b, eps):
-    y, mean, rstd = C().layernorm_fwd(s2, _bf16(ln_w), _bf16(ln_b), float(eps))
+    y, mean, rstd = C().layernorm_fwd(s2, as_bf16(ln_w), as_bf16(ln_b), float(eps))
     ctx.ln = (mean, rstd)
-    ctx.has_ln_bias = ln_b is not None
-    ctx.ln_b_dtype = None if ln_b is None else ln_b.dtype
     return y
+
+
+def _rows(g, s2):
+    return None if g is None else g.reshape(s2.shape)
 
 
 def _ln_backward(ctx, s2, ln_w, ln_b, rb, ds, dy):
     """LayerNorm backward of y = LN(s) plus the stream gradient ds arriving from later sites:
     returns (dsum = d(s) total, dW_ln, db_ln, d rb) with rb's gradient = colsum(dsum)."""
-    mean, rstd = ctx.ln
-    if dy is None:
-        dy = torch.zeros_like(s2)
-    dres = None if ds is None else ds.reshape(s2.shape).contiguous()
-    sw, sb, srb = _claim((ln_w, ln_b, rb))
-    dsum, dw, db, drb = C().layernorm_bwd(dy.reshape(s2.shape).contiguous(), s2, _bf16(ln_w), mean, rstd,
-                                          ctx.has_ln_bias, dres, True, _view(sw), _view(sb), _view(srb))
-    _notify(sw, sb, srb)
-    dw, db, drb = _unless(dw, sw), _unless(db, sb), _unless(drb, srb)
-    return (dsum, _grad(dw, ln_w.dtype), (_grad(db, ctx.ln_b_dtype) if ctx.has_ln_bias else None),
-            _grad(drb, rb.dtype))
+    return layer_norm_backward(_rows(dy, s2), s2, *ctx.ln, ln_w, ln_b, dres=_rows(ds, s2), rb=rb)
 
 
 class _LinearResidualLN(torch.autograd.Function):
@@ -168,19 +161,13 @@ def mlp_eligible(x, h, w_fc, w_proj, b_proj) -> bool:
 
 # ---------------------------------------------------------------- Llama: RMSNorm sites (no biases)
 def _rms_forward(ctx, s2, w, eps):
-    y, rstd = C().rmsnorm_fwd(s2, _bf16(w), float(eps))
+    y, rstd = C().rmsnorm_fwd(s2, as_bf16(w), float(eps))
     ctx.rstd = rstd
     return y
 
 
 def _rms_backward(ctx, s2, w, ds, dy):
-    if dy is None:
-        dy = torch.zeros_like(s2)
-    dres = None if ds is None else ds.reshape(s2.shape).contiguous()
-    (sw,) = _claim((w,))
-    dsum, dw = C().rmsnorm_bwd(dy.reshape(s2.shape).contiguous(), s2, _bf16(w), ctx.rstd, dres, _view(sw))
-    _notify(sw)
-    return dsum, _grad(_unless(dw, sw), w.dtype)
+    return rms_norm_backward(_rows(dy, s2), s2, ctx.rstd, w, dres=_rows(ds, s2))
 
 
 class _LinearResidualRMS(torch.autograd.Function):

@@ -14,8 +14,9 @@ from __future__ import annotations
 import torch
 
 from ._ext import C
-from .gemm import WGRAD_FIRST, linear_dgrad, linear_fwd, wgrad, wgrad_into
+from .gemm import WGRAD_FIRST, linear_dgrad, linear_fwd, weight_grad
 from .grad_sink import sink_of
+from .linear import grads_in_order
 
 import os
 
@@ -39,20 +40,13 @@ class _LinearXent(torch.autograd.Function):
     def backward(ctx, g):
         x, w, dl = ctx.saved_tensors
         s = g.detach().float().reshape(1).contiguous()
-        dx = dw = None
-        if ctx.needs_input_grad[0] and not _LM_WGRAD_FIRST:
+
+        def dgrad():
             dx = linear_dgrad(dl, w)
             C().scale_(dx, s)
-        if ctx.needs_input_grad[1]:
-            sink = ctx.sink
-            if sink is not None:
-                wgrad_into(dl, x, sink.view, sink.take(), s)
-                sink.notify()
-            else:
-                dw = wgrad(dl, x, s)
-        if ctx.needs_input_grad[0] and _LM_WGRAD_FIRST:
-            dx = linear_dgrad(dl, w)
-            C().scale_(dx, s)
+            return dx
+        dx, dw = grads_in_order(dgrad, lambda: weight_grad(dl, x, ctx.sink, s),
+                                ctx.needs_input_grad[0], ctx.needs_input_grad[1], _LM_WGRAD_FIRST)
         return dx, dw, None, None
 
 
@@ -140,18 +134,9 @@ class _LinearXentExp(torch.autograd.Function):
         if xt:
             xs = xs.t()  # (N, C) view of the (C, N) tensor
         one = torch.ones(1, dtype=torch.float32, device=x.device)
-        dx = dw = None
-        if ctx.needs_input_grad[0] and not _LM_WGRAD_FIRST:
-            dx = C().gemm_rowscale(e, w, srow)
-        if ctx.needs_input_grad[1]:
-            sink = ctx.sink
-            if sink is not None:
-                wgrad_into(e, xs, sink.view, sink.take(), one)
-                sink.notify()
-            else:
-                dw = wgrad(e, xs, one)
-        if ctx.needs_input_grad[0] and _LM_WGRAD_FIRST:
-            dx = C().gemm_rowscale(e, w, srow)
+        dx, dw = grads_in_order(lambda: C().gemm_rowscale(e, w, srow),
+                                lambda: weight_grad(e, xs, ctx.sink, one),
+                                ctx.needs_input_grad[0], ctx.needs_input_grad[1], _LM_WGRAD_FIRST)
         return dx, dw, None, None
 
 

@@ -154,15 +154,20 @@ def test_fused_mlp_tail_matches_two_node_path(fuse_out_bias, monkeypatch):
         assert rel_err(x, y) < 1e-2, (name, rel_err(x, y))
 
 
-@pytest.mark.parametrize("proj_bias", [False, True])
-@pytest.mark.parametrize("fc_bias", [True, False])
-def test_fused_mlp_matches_reference(proj_bias, fc_bias, monkeypatch):
+@pytest.mark.parametrize("fc_bias,proj_bias,order", [
+    (True, False, None), (True, True, None), (False, False, None), (False, True, None),
+    (True, True, "0"), (True, True, "2")],
+    ids=["True-False", "True-True", "False-False", "False-True", "order0", "order2"])
+def test_fused_mlp_matches_reference(proj_bias, fc_bias, order, monkeypatch):
     """ops.mlp on the GPU path with ORION_FUSED_MLP (bias + GELU in the fc GEMM's epilogue,
     GELU' + fc-bias column sums in the projection's input-gradient GEMM) against fp32 autograd
-    of linear -> GELU-tanh -> linear: output and every gradient, ragged token count."""
+    of linear -> GELU-tanh -> linear: output and every gradient, ragged token count; the
+    backward's GEMMs in the configured order (None) and in the other two (_MLP_BWD_ORDER)."""
     from orion_amd import ops
     from orion_amd.ops import activations
     monkeypatch.setattr(activations, "_FUSED_MLP", True)
+    if order is not None:
+        monkeypatch.setattr(activations, "_MLP_BWD_ORDER", order)
     g = torch.Generator(device=DEV).manual_seed(5)
     x = _rnd(g, 3, 333, 256)
     wfc, bfc = _rnd(g, 1024, 256) * 0.1, _rnd(g, 1024)
@@ -295,12 +300,17 @@ def test_gemm_swiglu_bwd_epilogue(M, C_, F_, gemm_cfg):
     within_bf16_budget("dup", got[:, F_:], gr.grad[:, F_:], gb.grad[:, F_:])
 
 
-@pytest.mark.parametrize("F_", [1376, 1408])
-def test_swiglu_mlp_matches_reference(F_):
+@pytest.mark.parametrize("F_,order", [(1376, None), (1408, None), (1408, "1"), (1408, "2")],
+                         ids=["1376", "1408", "1408-order1", "1408-order2"])
+def test_swiglu_mlp_matches_reference(F_, order, monkeypatch):
     """ops.swiglu_mlp (Llama feed-forward, SwiGLU backward fused into the down_proj input
     gradient GEMM; F = 1408 also the SwiGLU forward in the gate_up GEMM's epilogue, 1376 the
-    swiglu pass) against fp32 autograd: output and every gradient, ragged token count."""
+    swiglu pass) against fp32 autograd: output and every gradient, ragged token count; the
+    backward's GEMMs in the configured order (None) and in the other two (_SWIGLU_BWD_ORDER)."""
     from orion_amd import ops
+    from orion_amd.ops import activations
+    if order is not None:
+        monkeypatch.setattr(activations, "_SWIGLU_BWD_ORDER", order)
     g = torch.Generator(device=DEV).manual_seed(9)
     x = _rnd(g, 3, 111, 512)
     wgu, wd = _rnd(g, 2 * F_, 512) * 0.1, _rnd(g, 512, F_) * 0.05
@@ -319,6 +329,31 @@ def test_swiglu_mlp_matches_reference(F_):
     within_bf16_budget("y", y, yr, yb)
     for n, t, f, b in zip(("dx", "dwgu", "dwdown"), ts, fs, bs):
         within_bf16_budget(n, t.grad, f.grad, b.grad)
+
+
+@pytest.mark.parametrize("wgrad_first", [False, True])
+def test_linear_with_bias_matches_reference(wgrad_first, monkeypatch):
+    """ops.linear on the in-tree GEMMs with a bias, the weight gradient after (default) and
+    before the input gradient (ops.gemm.WGRAD_FIRST; the bias column sum moves with it):
+    96 rows and K = 128, the smallest the in-tree weight- and input-gradient kernels take."""
+    from orion_amd import ops
+    from orion_amd.ops import gemm
+    monkeypatch.setattr(gemm, "WGRAD_FIRST", wgrad_first)
+    g = torch.Generator(device=DEV).manual_seed(17)
+    x, w, b = _rnd(g, 2, 48, 128), _rnd(g, 192, 128), _rnd(g, 192)
+    dy = _rnd(g, 2, 48, 192)
+    ts = [t.clone().requires_grad_() for t in (x, w, b)]
+    y = ops.linear(*ts)
+    y.backward(dy)
+    fs = [t.detach().float().requires_grad_() for t in (x, w, b)]
+    yr = torch.nn.functional.linear(*fs)
+    yr.backward(dy.float())
+    bs = [t.detach().clone().requires_grad_() for t in (x, w, b)]
+    yb = torch.nn.functional.linear(*bs)
+    yb.backward(dy)
+    within_bf16_budget("y", y, yr, yb)
+    for n, t, f, bb in zip(("dx", "dw", "db"), ts, fs, bs):
+        within_bf16_budget(n, t.grad, f.grad, bb.grad)
 
 
 def test_per_item_walk_is_bitwise_identical():
