@@ -1090,26 +1090,27 @@ Tensor kv_append(const Tensor& k_new, const Tensor& v_new, Tensor k_cache, Tenso
 }
 
 // ------------------------------------------------------------------ decode linear (csrc/linear_decode.hip)
-// y (M, Nout) = epi(pro(x) (M, K) . w (N, K)^T) for M <= 16: norm 0 none / 1 LayerNorm / 2 RMSNorm
-// on the rows of x, act 0 none / 1 GELU-tanh / 2 SwiGLU over a packed [gate; up] weight (N = 2 Nout),
-// then + residual.  Written into `out` when given (a static buffer of a captured step).
-Tensor linear_decode(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& bias, int64_t norm,
-                     const c10::optional<Tensor>& norm_w, const c10::optional<Tensor>& norm_b, double eps,
-                     int64_t act, const c10::optional<Tensor>& residual, c10::optional<Tensor> out) {
-  check_bf16(x, "x"); check_bf16(w, "weight");
-  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == w.size(1), "linear_decode: x (M, K) and weight (N, K), got ",
+// What the bf16 and the FP8 op share: every check but the weight's dtype, and every field of the
+// parameter block P but the weight's.  K must be a multiple of `kmult`; returns y.
+template <class P>
+Tensor linear_decode_args(P& p, const char* op, int64_t kmult, const Tensor& x, const Tensor& w,
+                          const c10::optional<Tensor>& bias, int64_t norm, const c10::optional<Tensor>& norm_w,
+                          const c10::optional<Tensor>& norm_b, double eps, int64_t act,
+                          const c10::optional<Tensor>& residual, const c10::optional<Tensor>& out) {
+  check_bf16(x, "x");
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == w.size(1), op, ": x (M, K) and weight (N, K), got ",
               x.sizes(), " and ", w.sizes());
   const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
-  TORCH_CHECK(M >= 1 && M <= 16, "linear_decode: 1 <= M <= 16 rows, got ", M);
-  TORCH_CHECK(K >= 8 && K % 8 == 0, "linear_decode: K must be a positive multiple of 8, got ", K);
-  TORCH_CHECK(norm >= 0 && norm <= 2 && act >= 0 && act <= 2, "linear_decode: unknown norm / act selector");
-  TORCH_CHECK(N >= 1 && (act != orion::LD_ACT_SWIGLU || N % 2 == 0), "linear_decode: SwiGLU needs an even number of weight rows");
-  TORCH_CHECK(N < (1LL << 31) && K < (1LL << 31), "linear_decode: weight too large");
-  TORCH_CHECK(w.is_contiguous() && (uintptr_t)w.data_ptr() % 16 == 0, "linear_decode: weight must be contiguous and 16-byte aligned");
+  TORCH_CHECK(M >= 1 && M <= 16, op, ": 1 <= M <= 16 rows, got ", M);
+  TORCH_CHECK(K >= kmult && K % kmult == 0, op, ": K must be a positive multiple of ", kmult, ", got ", K);
+  TORCH_CHECK(norm >= 0 && norm <= 2 && act >= 0 && act <= 2, op, ": unknown norm / act selector");
+  TORCH_CHECK(N >= 1 && (act != orion::LD_ACT_SWIGLU || N % 2 == 0), op, ": SwiGLU needs an even number of weight rows");
+  TORCH_CHECK(N < (1LL << 31) && K < (1LL << 31), op, ": weight too large");
+  TORCH_CHECK(w.is_contiguous() && (uintptr_t)w.data_ptr() % 16 == 0, op, ": weight must be contiguous and 16-byte aligned");
   auto rows_ok = [](const Tensor& t) {
     return t.stride(1) == 1 && (t.size(0) == 1 || t.stride(0) % 8 == 0) && (uintptr_t)t.data_ptr() % 16 == 0;
   };
-  TORCH_CHECK(rows_ok(x), "linear_decode: rows of x must be 16-byte aligned with unit stride (misaligned rows)");
+  TORCH_CHECK(rows_ok(x), op, ": rows of x must be 16-byte aligned with unit stride (misaligned rows)");
   TORCH_CHECK(w.device() == x.device(), "device mismatch");
   const int64_t Nout = act == orion::LD_ACT_SWIGLU ? N / 2 : N;
   auto vec = [&](const c10::optional<Tensor>& t, int64_t n, const char* name) -> const unsigned short* {
@@ -1117,22 +1118,21 @@ Tensor linear_decode(const Tensor& x, const Tensor& w, const c10::optional<Tenso
     check_bf16(*t, name);
     TORCH_CHECK(t->dim() == 1 && t->size(0) == n && t->is_contiguous() && t->device() == x.device() &&
                     (uintptr_t)t->data_ptr() % 16 == 0,
-                "linear_decode: ", name, " must be a contiguous 16-byte aligned vector of ", n);
+                op, ": ", name, " must be a contiguous 16-byte aligned vector of ", n);
     return (const unsigned short*)t->data_ptr();
   };
-  orion::LinearDecodeParams p{};
   p.bias = vec(bias, N, "bias");
   p.norm_w = vec(norm_w, K, "norm_weight");
   p.norm_b = vec(norm_b, K, "norm_bias");
-  TORCH_CHECK((norm != orion::LD_NORM_NONE) == (p.norm_w != nullptr), "linear_decode: norm_weight comes with a norm");
-  TORCH_CHECK(norm == orion::LD_NORM_LAYER || !p.norm_b, "linear_decode: norm_bias is LayerNorm's");
+  TORCH_CHECK((norm != orion::LD_NORM_NONE) == (p.norm_w != nullptr), op, ": norm_weight comes with a norm");
+  TORCH_CHECK(norm == orion::LD_NORM_LAYER || !p.norm_b, op, ": norm_bias is LayerNorm's");
   c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
   Tensor y;
   if (given(out)) {
     y = *out;
     check_bf16(y, "out");
     TORCH_CHECK(y.dim() == 2 && y.size(0) == M && y.size(1) == Nout && y.stride(1) == 1 && y.device() == x.device(),
-                "linear_decode: out must be (M, Nout) with unit column stride");
+                op, ": out must be (M, Nout) with unit column stride");
   } else {
     y = at::empty({M, Nout}, x.options());
   }
@@ -1143,23 +1143,56 @@ Tensor linear_decode(const Tensor& x, const Tensor& w, const c10::optional<Tenso
     const char* b1 = b0 + ((t.size(0) - 1) * t.stride(0) + t.size(1)) * 2;
     return a0 < b1 && b0 < a1;
   };
-  TORCH_CHECK(!overlaps(x), "linear_decode: out aliases x");
+  TORCH_CHECK(!overlaps(x), op, ": out aliases x");
   if (given(residual)) {
     const Tensor& r = *residual;
     check_bf16(r, "residual");
     TORCH_CHECK(r.dim() == 2 && r.size(0) == M && r.size(1) == Nout && r.stride(1) == 1 && r.device() == x.device(),
-                "linear_decode: residual must be (M, Nout) with unit column stride");
-    TORCH_CHECK(!overlaps(r), "linear_decode: residual aliases the output (it must be a distinct tensor)");
+                op, ": residual must be (M, Nout) with unit column stride");
+    TORCH_CHECK(!overlaps(r), op, ": residual aliases the output (it must be a distinct tensor)");
     p.res = (const unsigned short*)r.data_ptr();
     p.res_rs = r.stride(0);
   }
   p.x = (const unsigned short*)x.data_ptr();
-  p.w = (const unsigned short*)w.data_ptr();
   p.y = (unsigned short*)y.data_ptr();
   p.x_rs = x.stride(0); p.y_rs = y.stride(0);
   p.M = (int)M; p.K = (int)K; p.Nout = (int)Nout;
   p.norm = (int)norm; p.act = (int)act; p.eps = (float)eps;
+  return y;
+}
+
+// y (M, Nout) = epi(pro(x) (M, K) . w (N, K)^T) for M <= 16: norm 0 none / 1 LayerNorm / 2 RMSNorm
+// on the rows of x, act 0 none / 1 GELU-tanh / 2 SwiGLU over a packed [gate; up] weight (N = 2 Nout),
+// then + residual.  Written into `out` when given (a static buffer of a captured step).
+Tensor linear_decode(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& bias, int64_t norm,
+                     const c10::optional<Tensor>& norm_w, const c10::optional<Tensor>& norm_b, double eps,
+                     int64_t act, const c10::optional<Tensor>& residual, c10::optional<Tensor> out) {
+  check_bf16(x, "x"); check_bf16(w, "weight");
+  orion::LinearDecodeParams p{};
+  Tensor y = linear_decode_args(p, "linear_decode", 8, x, w, bias, norm, norm_w, norm_b, eps, act, residual, out);
+  p.w = (const unsigned short*)w.data_ptr();
   check_launch(orion_linear_decode(p, cur_stream()), "linear_decode");
+  return y;
+}
+
+// ------------------------------------------------------------------ FP8 decode linear (csrc/linear_decode_fp8.hip)
+// linear_decode with the weight as OCP e4m3fn bytes wq (N, K) and one fp32 scale per row:
+// W[n, k] = w_scale[n] wq[n, k]; x, bias, the norm vectors, residual and out stay bf16.
+Tensor linear_decode_fp8(const Tensor& x, const Tensor& wq, const Tensor& w_scale, const c10::optional<Tensor>& bias,
+                         int64_t norm, const c10::optional<Tensor>& norm_w, const c10::optional<Tensor>& norm_b,
+                         double eps, int64_t act, const c10::optional<Tensor>& residual, c10::optional<Tensor> out) {
+  check_bf16(x, "x");
+  TORCH_CHECK(wq.is_cuda(), "weight must be a GPU tensor");
+  TORCH_CHECK(wq.scalar_type() == at::kFloat8_e4m3fn, "linear_decode_fp8: weight must be Float8_e4m3fn (OCP e4m3, ",
+              "the gfx950 format), got ", wq.scalar_type());
+  orion::LinearDecodeFp8Params p{};
+  Tensor y = linear_decode_args(p, "linear_decode_fp8", 16, x, wq, bias, norm, norm_w, norm_b, eps, act, residual, out);
+  TORCH_CHECK(w_scale.is_cuda() && w_scale.device() == x.device() && w_scale.scalar_type() == at::kFloat &&
+                  w_scale.dim() == 1 && w_scale.size(0) == wq.size(0) && w_scale.is_contiguous(),
+              "linear_decode_fp8: w_scale must be a contiguous float32 vector of ", wq.size(0), " on x's device");
+  p.wq = (const unsigned char*)wq.data_ptr();
+  p.w_scale = w_scale.data_ptr<float>();
+  check_launch(orion_linear_decode_fp8(p, cur_stream()), "linear_decode_fp8");
   return y;
 }
 
@@ -1276,6 +1309,7 @@ TORCH_LIBRARY(orion_amd, m) {
   m.def("attn_decode(Tensor q, Tensor k_cache, Tensor v_cache, Tensor kv_lens, float scale, int splits=0) -> Tensor");
   m.def("kv_append(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor kv_lens, Tensor? q=None, Tensor? cos=None, Tensor? sin=None) -> Tensor");
   m.def("linear_decode(Tensor x, Tensor w, Tensor? bias, int norm, Tensor? norm_w, Tensor? norm_b, float eps, int act, Tensor? residual, Tensor(a!)? out=None) -> Tensor");
+  m.def("linear_decode_fp8(Tensor x, Tensor wq, Tensor w_scale, Tensor? bias, int norm, Tensor? norm_w, Tensor? norm_b, float eps, int act, Tensor? residual, Tensor(a!)? out=None) -> Tensor");
   m.def("sample_tokens(Tensor logits, Tensor params, Tensor? u, Tensor? seed, Tensor? positions, Tensor(a!)? out=None, Tensor(b!)? history=None, Tensor(c!)? u_out=None) -> Tensor");
 }
 
@@ -1317,5 +1351,6 @@ TORCH_LIBRARY_IMPL(orion_amd, CUDA, m) {
   m.impl("attn_decode", &attn_decode);
   m.impl("kv_append", &kv_append);
   m.impl("linear_decode", &linear_decode);
+  m.impl("linear_decode_fp8", &linear_decode_fp8);
   m.impl("sample_tokens", &sample_tokens);
 }

@@ -31,6 +31,7 @@
 //     8-element fragment is inside or outside as a whole); padded fragments are zeros.
 #include "common.h"
 #include "launchers.h"
+#include "linear_decode_mfma.h"
 
 namespace orion {
 
@@ -40,17 +41,6 @@ namespace {
 constexpr int LD_NW_WIDE = 8, LD_U_WIDE = 8;  // plain projections with K >= LD_K_WIDE
 constexpr int LD_NW = 4, LD_U = 4;            // the others
 constexpr int LD_K_WIDE = 32 * LD_NW_WIDE * LD_U_WIDE;  // one full round of the wide form
-
-ORION_DEVICE f32x4 ld_mfma(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_mfma, a),
-                                                 __builtin_bit_cast(bf16x8_mfma, b), c, 0, 0, 0);
-}
-
-ORION_DEVICE float sum16(float v) {  // over the aligned group of 16 lanes, every lane the total
-#pragma unroll
-  for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 template <int NORM, int NB, int U>
 struct LdStage {

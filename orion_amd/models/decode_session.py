@@ -36,29 +36,52 @@ class DecodeSession:
     (temperature bits, top-k) and ``history`` (batch, max_len + 1) int64, and with ``graph=True``
     a second graph, the step followed by the sampling launch, that writes each new token into
     ``tokens`` for the next replay.  ``step`` and its step-only graph do not change; a session
-    holds at most one graph of each kind."""
+    holds at most one graph of each kind.
 
-    def __init__(self, model, batch, max_len=None, graph=False, sampler="torch"):
+    ``weights="fp8"`` quantises every weight of ``model.decode_projections()``, the LM head
+    included, once at construction (``ops.quantize_fp8``: e4m3 bytes and one fp32 scale per row)
+    and keeps them as ``qweights``, name -> ``ops.Fp8Weight``; ``weight_bytes`` is what they
+    hold.  The step then streams those bytes (csrc/linear_decode_fp8.hip) and the prefill runs
+    on their dequantised values, so the prompt and the generated tokens see one model.  The
+    model's parameters are not modified and the embedding tables stay as they are (GPT-2's tied
+    ``wte`` is quantised as the head only); activations, the cache, attention and sampling do
+    not change.  With the default ``"bf16"``, ``qweights`` is None, ``weight_bytes`` counts the
+    model's own projection weights and the models are called exactly as without the keyword."""
+
+    def __init__(self, model, batch, max_len=None, graph=False, sampler="torch", weights="bf16"):
         if sampler not in ("torch", "device"):
             raise ValueError(f"sampler must be 'torch' or 'device', got {sampler!r}")
+        if weights not in ("bf16", "fp8"):
+            raise ValueError(f"weights must be 'bf16' or 'fp8', got {weights!r}")
         cfg = model.config
         self.model = model
         self.batch = int(batch)
         w = model.lm_head.weight
         self.on_gpu = w.is_cuda
         self.graph = bool(graph)
+        self.weights = weights
+        self.qweights = None
+        projections = list(model.decode_projections())
+        if weights == "fp8":
+            self.qweights = {name: ops.quantize_fp8(pw) for name, pw in projections}
+            projections = list(self.qweights.items())
+        self.weight_bytes = sum(pw.nbytes for _, pw in projections)
+        # what the model's calls get beyond their usual arguments: nothing for a bf16 session
+        self._model_kw = {} if self.qweights is None else {"weights": self.qweights}
         if self.graph and self.on_gpu:
             if self.batch > MAX_GRAPH_BATCH:
                 raise ValueError(f"DecodeSession(graph=True): batch {self.batch} > {MAX_GRAPH_BATCH}, the most "
                                  "rows the skinny linear kernel takes")
             probes = {}  # one input of the step's shape per K
-            for name, pw in model.decode_projections():
+            for name, pw in projections:
                 K = pw.shape[1]
                 if K not in probes:
                     probes[K] = torch.empty(self.batch, K, device=w.device, dtype=w.dtype)
                 if not ops.linear_decode_eligible(probes[K], pw):
-                    raise ValueError(f"DecodeSession(graph=True): {name} {tuple(pw.shape)} {pw.dtype} is not "
-                                     "eligible for ops.linear_decode (bf16 on the HIP backend, K % 8 == 0, "
+                    kind = (f"{pw.dtype}", "K % 8 == 0") if self.qweights is None else \
+                        ("fp8 (e4m3, bf16 activations)", "K % 16 == 0")
+                    raise ValueError(f"DecodeSession(graph=True): {name} {tuple(pw.shape)} {kind[0]} is not "
+                                     f"eligible for ops.linear_decode (bf16 on the HIP backend, {kind[1]}, "
                                      "contiguous weight), and a library GEMM must not be captured")
         self.cache = model.new_cache(self.batch, max_len)  # at most the model's context limit
         self.max_len = self.cache.max_len
@@ -81,7 +104,7 @@ class DecodeSession:
     def prefill(self, idx):
         """The model's ``forward_cached`` on this session's cache: logits (B, vocab) of the last
         position of ``idx`` (B, T); call it again for a chunked prompt."""
-        return self.model.forward_cached(idx, self.cache)
+        return self.model.forward_cached(idx, self.cache, **self._model_kw)
 
     def reset(self):
         """Empty the cache for a new prompt; a captured graph stays valid (same buffers)."""
@@ -94,7 +117,7 @@ class DecodeSession:
         cache = self.cache
         cache.start.copy_(cache.lens)
         cache.lens.add_(1)
-        self.model.decode_step(self.tokens, cache, self.logits)
+        self.model.decode_step(self.tokens, cache, self.logits, **self._model_kw)
 
     def _capture(self, body, restore):
         """``body`` as a graph.  An eager warm-up on a side stream first (lazy initialisations must

@@ -8,6 +8,23 @@ from __future__ import annotations
 
 import torch
 
+from ..ops.fp8 import Fp8Weight
+
+
+def session_weights(model, weights):
+    """The weights of ``model.decode_projections()`` in that order, each replaced by the entry of
+    the mapping ``weights`` (name -> ``ops.Fp8Weight``) that carries its name; None without a
+    mapping, and the caller then reads the parameters as it always did."""
+    if weights is None:
+        return None
+    return [weights.get(name, p) for name, p in model.decode_projections()]
+
+
+def dense(weight, dtype):
+    """A weight that the plain ops take: an ``ops.Fp8Weight`` dequantised to ``dtype`` (a transient),
+    anything else as it is."""
+    return weight.dequant(dtype) if isinstance(weight, Fp8Weight) else weight
+
 
 def sample_logits(logits, temperature=1.0, top_k=None):
     """The models' sampling rule on (B, vocab) logits -> (B, 1) token ids: temperature, the top-k
@@ -22,14 +39,16 @@ def sample_logits(logits, temperature=1.0, top_k=None):
 class Generation:
     """``generate`` and ``decode_session`` of a model with a :class:`KVCache`."""
 
-    def decode_session(self, batch, max_len=None, graph=False, sampler="torch"):
+    def decode_session(self, batch, max_len=None, graph=False, sampler="torch", weights="bf16"):
         """A :class:`DecodeSession` for this model: the fused decode step, captured when ``graph``;
-        ``sampler="device"`` draws the tokens with ``ops.sample_tokens`` inside that step."""
+        ``sampler="device"`` draws the tokens with ``ops.sample_tokens`` inside that step and
+        ``weights="fp8"`` decodes from per-row e4m3 copies of the projection weights."""
         from .decode_session import DecodeSession
-        return DecodeSession(self, batch, max_len, graph=graph, sampler=sampler)
+        return DecodeSession(self, batch, max_len, graph=graph, sampler=sampler, weights=weights)
 
     @torch.no_grad()
-    def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, use_cache=False, sampler="torch"):
+    def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, use_cache=False, sampler="torch",
+                 weights="bf16"):
         """nanoGPT's sampling loop.  ``use_cache=True`` keeps every layer's keys / values
         (:class:`KVCache`): the prompt is prefilled once and each new token costs one single-token
         forward.  Tokens beyond the context limit (``block_size`` / ``max_seq_len``) take the
@@ -38,7 +57,10 @@ class Generation:
         :class:`DecodeSession` (the fused skinny-linear decode step), ``"graph"`` additionally
         replays that step from one captured HIP graph.  With either, ``sampler="device"`` draws
         the session's tokens with ``ops.sample_tokens`` inside the step (seeded from torch's
-        default generator) instead of stock torch ops between the steps."""
+        default generator) instead of stock torch ops between the steps, and ``weights="fp8"``
+        makes the session quantise the projection weights once (``ops.quantize_fp8``) and run the
+        prompt and every cached token on them.  The sliding-window loop beyond the context limit
+        keeps using the model's own (unquantised) weights, as it keeps clear of the session."""
         fused = isinstance(use_cache, str)
         if fused and use_cache not in ("fused", "graph"):
             raise ValueError(f"use_cache must be False, True, 'fused' or 'graph', got {use_cache!r}")
@@ -47,12 +69,18 @@ class Generation:
         if sampler == "device" and not fused:
             raise ValueError("sampler='device' samples inside the fused decode step: use_cache must be 'fused' "
                              f"or 'graph', got {use_cache!r}")
+        if weights not in ("bf16", "fp8"):
+            raise ValueError(f"weights must be 'bf16' or 'fp8', got {weights!r}")
+        if weights == "fp8" and not fused:
+            raise ValueError("weights='fp8' decodes through the fused decode step: use_cache must be 'fused' "
+                             f"or 'graph', got {use_cache!r}")
         limit = self.context_len
         B, T = idx.shape
         if use_cache and max_new_tokens > 0 and T < limit:
             n = min(max_new_tokens, limit - T + 1)  # the n-th token is drawn from position limit - 1's logits
             if fused:
-                sess = self.decode_session(B, T + n - 1, graph=use_cache == "graph", sampler=sampler)
+                sess = self.decode_session(B, T + n - 1, graph=use_cache == "graph", sampler=sampler,
+                                           weights=weights)
                 idx = sess.generate(idx, n, temperature, top_k)
             else:
                 cache = self.new_cache(B, T + n - 1)

@@ -24,7 +24,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
-from .generation import Generation
+from .generation import Generation, dense, session_weights
 from .kv_cache import KVCache
 
 
@@ -215,11 +215,14 @@ class GPT(nn.Module, Generation):
                        cfg.head_dim, device=w.device, dtype=w.dtype)
 
     @torch.no_grad()
-    def forward_cached(self, idx, cache):
+    def forward_cached(self, idx, cache, weights=None):
         """Logits (B, vocab) of the last position of ``idx`` (B, T), given the ``cache.pos`` tokens
         already in ``cache``; appends this call's keys / values.  T > 1 is a (chunked) prefill
         through the flash forward, T == 1 a decode step through ``ops.attention_decode``.  Plain
-        ops throughout: the training-time fused residual sites have no place at M = B."""
+        ops throughout: the training-time fused residual sites have no place at M = B.
+        ``weights`` maps names of :meth:`decode_projections` to ``ops.Fp8Weight``: such a
+        projection runs on its dequantised weight, one transient at a time (the embedding tables
+        stay the model's)."""
         B, T = idx.shape
         cfg, tr = self.config, self.transformer
         assert cache.pos + T <= cfg.block_size, f"sequence {cache.pos + T} > block_size {cfg.block_size}"
@@ -228,9 +231,12 @@ class GPT(nn.Module, Generation):
         H, D = cfg.n_head, cfg.head_dim
         x = ops.add_broadcast(F.embedding(idx, tr.wte.weight), tr.wpe.weight[pos:pos + T])
         h = blocks[0].ln_1(x)
+        ws = session_weights(self, weights)
         for i, block in enumerate(blocks):
             at, ml = block.attn, block.mlp
-            qkv = ops.linear(h, at.c_attn.weight, at.c_attn.bias).view(B, T, 3, H, D)
+            w_qkv, w_o, w_fc, w_pr = (at.c_attn.weight, at.c_proj.weight, ml.c_fc.weight, ml.c_proj.weight) \
+                if ws is None else ws[4 * i:4 * i + 4]
+            qkv = ops.linear(h, dense(w_qkv, h.dtype), at.c_attn.bias).view(B, T, 3, H, D)
             kc, vc = cache.layer(i)
             ops.kv_append(qkv[:, :, 1], qkv[:, :, 2], kc, vc, cache.start)
             end = pos + T  # the host's bound of the length: the key split is planned from it
@@ -238,12 +244,13 @@ class GPT(nn.Module, Generation):
                 y = ops.attention_decode(qkv[:, 0, 0], kc[:, :end], vc[:, :end], cache.lens)
             else:
                 y = ops.attention(qkv[:, :, 0], kc[:, :end], vc[:, :end], causal=True)
-            a = ops.linear(y.reshape(B, T, H * D), at.c_proj.weight, at.c_proj.bias)
+            a = ops.linear(y.reshape(B, T, H * D), dense(w_o, h.dtype), at.c_proj.bias)
             x, h = ops.add_layer_norm(x, a, block.ln_2.weight, block.ln_2.bias)
-            m = ops.mlp(h, ml.c_fc.weight, ml.c_fc.bias, ml.c_proj.weight, ml.c_proj.bias)
+            m = ops.mlp(h, dense(w_fc, h.dtype), ml.c_fc.bias, dense(w_pr, h.dtype), ml.c_proj.bias)
             nxt = blocks[i + 1].ln_1 if i + 1 < len(blocks) else tr.ln_f
             x, h = ops.add_layer_norm(x, m, nxt.weight, nxt.bias)
-        return ops.linear(h[:, -1, :].contiguous(), self.lm_head.weight)
+        w_head = self.lm_head.weight if ws is None else ws[-1]
+        return ops.linear(h[:, -1, :].contiguous(), dense(w_head, h.dtype))
 
     def decode_projections(self):
         """(name, weight) of every projection of :meth:`decode_step`."""
@@ -254,27 +261,32 @@ class GPT(nn.Module, Generation):
             yield f"h.{i}.mlp.c_proj", blk.mlp.c_proj.weight
         yield "lm_head", self.lm_head.weight
 
-    def decode_step(self, tokens, cache, logits_out):
+    def decode_step(self, tokens, cache, logits_out, weights=None):
         """:meth:`forward_cached` at T = 1 for a :class:`DecodeSession`, on device state only:
         the logits of ``tokens`` (B, 1) at position ``cache.start`` go into ``logits_out``.  Every
         projection is one ``ops.linear_decode`` with the norm in its prologue and the bias /
-        GELU / residual in its epilogue; the session has advanced ``cache.start`` / ``cache.lens``."""
+        GELU / residual in its epilogue; the session has advanced ``cache.start`` / ``cache.lens``.
+        A projection named in ``weights`` (name -> ``ops.Fp8Weight``) streams that weight."""
         cfg, tr = self.config, self.transformer
         B, H, D = tokens.shape[0], cfg.n_head, cfg.head_dim
         x = F.embedding(tokens[:, 0], tr.wte.weight) + F.embedding(cache.start, tr.wpe.weight)
+        ws = session_weights(self, weights)
         for i, blk in enumerate(tr.h):
             at, ml = blk.attn, blk.mlp
-            qkv = ops.linear_decode(x, at.c_attn.weight, at.c_attn.bias, norm="layer", norm_weight=blk.ln_1.weight,
+            w_qkv, w_o, w_fc, w_pr = (at.c_attn.weight, at.c_proj.weight, ml.c_fc.weight, ml.c_proj.weight) \
+                if ws is None else ws[4 * i:4 * i + 4]
+            qkv = ops.linear_decode(x, w_qkv, at.c_attn.bias, norm="layer", norm_weight=blk.ln_1.weight,
                                     norm_bias=blk.ln_1.bias).view(B, 1, 3, H, D)
             kc, vc = cache.layer(i)
             ops.kv_append(qkv[:, :, 1], qkv[:, :, 2], kc, vc, cache.start)
             # the whole cache view: the key split is planned from max_len once and never changes
             y = ops.attention_decode(qkv[:, 0, 0], kc, vc, cache.lens)
-            x = ops.linear_decode(y.view(B, H * D), at.c_proj.weight, at.c_proj.bias, residual=x)
-            h = ops.linear_decode(x, ml.c_fc.weight, ml.c_fc.bias, norm="layer", norm_weight=blk.ln_2.weight,
+            x = ops.linear_decode(y.view(B, H * D), w_o, at.c_proj.bias, residual=x)
+            h = ops.linear_decode(x, w_fc, ml.c_fc.bias, norm="layer", norm_weight=blk.ln_2.weight,
                                   norm_bias=blk.ln_2.bias, act="gelu")
-            x = ops.linear_decode(h, ml.c_proj.weight, ml.c_proj.bias, residual=x)
-        ops.linear_decode(x, self.lm_head.weight, norm="layer", norm_weight=tr.ln_f.weight, norm_bias=tr.ln_f.bias,
+            x = ops.linear_decode(h, w_pr, ml.c_proj.bias, residual=x)
+        w_head = self.lm_head.weight if ws is None else ws[-1]
+        ops.linear_decode(x, w_head, norm="layer", norm_weight=tr.ln_f.weight, norm_bias=tr.ln_f.bias,
                           out=logits_out)
 
 

@@ -25,7 +25,7 @@ import torch.nn.functional as F
 
 from .. import ops
 from ..ops import reference as ref
-from .generation import Generation
+from .generation import Generation, dense, session_weights
 from .kv_cache import KVCache
 
 
@@ -182,11 +182,14 @@ class Llama(nn.Module, Generation):
                        cfg.head_dim, device=w.device, dtype=w.dtype)
 
     @torch.no_grad()
-    def forward_cached(self, idx, cache):
+    def forward_cached(self, idx, cache, weights=None):
         """Logits (B, vocab) of the last position of ``idx`` (B, T), given the ``cache.pos`` tokens
         already in ``cache``; appends this call's rotated keys and values.  T > 1 is a (chunked)
         prefill through the flash forward, T == 1 a decode step through ``ops.attention_decode``.
-        Plain ops throughout: the training-time fused residual sites have no place at M = B."""
+        Plain ops throughout: the training-time fused residual sites have no place at M = B.
+        ``weights`` maps names of :meth:`decode_projections` to ``ops.Fp8Weight``: such a
+        projection runs on its dequantised weight, one transient at a time (the embedding table
+        stays the model's)."""
         B, T = idx.shape
         cfg = self.config
         assert cache.pos + T <= cfg.max_seq_len
@@ -197,9 +200,12 @@ class Llama(nn.Module, Generation):
         layers = self.layers
         x = ops.token_embedding(idx, self.embed_tokens.weight)
         h = layers[0].input_layernorm(x)
+        ws = session_weights(self, weights)
         for i, layer in enumerate(layers):
             at, ff, pln = layer.self_attn, layer.mlp, layer.post_attention_layernorm
-            qkv = ops.linear(h, at.qkv_proj.weight).view(B, T, Hq + 2 * Hkv, D)
+            w_qkv, w_o, w_gu, w_dn = (at.qkv_proj.weight, at.o_proj.weight, ff.gate_up_proj.weight,
+                                      ff.down_proj.weight) if ws is None else ws[4 * i:4 * i + 4]
+            qkv = ops.linear(h, dense(w_qkv, h.dtype)).view(B, T, Hq + 2 * Hkv, D)
             kc, vc = cache.layer(i)
             q = ops.kv_append(qkv[:, :, Hq:Hq + Hkv], qkv[:, :, Hq + Hkv:], kc, vc, cache.start,
                               q=qkv[:, :, :Hq], cos=cos, sin=sin)
@@ -207,12 +213,13 @@ class Llama(nn.Module, Generation):
                 y = ops.attention_decode(q[:, 0], kc[:, :end], vc[:, :end], cache.lens)
             else:
                 y = ops.attention(q, kc[:, :end], vc[:, :end], causal=True)
-            a = ops.linear(y.reshape(B, T, Hq * D), at.o_proj.weight)
+            a = ops.linear(y.reshape(B, T, Hq * D), dense(w_o, h.dtype))
             x, h = ops.add_rms_norm(x, a, pln.weight, pln.eps)
-            m = ops.swiglu_mlp(h, ff.gate_up_proj.weight, ff.down_proj.weight)
+            m = ops.swiglu_mlp(h, dense(w_gu, h.dtype), dense(w_dn, h.dtype))
             nxt = layers[i + 1].input_layernorm if i + 1 < len(layers) else self.norm
             x, h = ops.add_rms_norm(x, m, nxt.weight, nxt.eps)
-        return ops.linear(h[:, -1, :].contiguous(), self.lm_head.weight)
+        w_head = self.lm_head.weight if ws is None else ws[-1]
+        return ops.linear(h[:, -1, :].contiguous(), dense(w_head, h.dtype))
 
     def decode_projections(self):
         """(name, weight) of every projection of :meth:`decode_step`."""
@@ -223,29 +230,34 @@ class Llama(nn.Module, Generation):
             yield f"layers.{i}.mlp.down_proj", layer.mlp.down_proj.weight
         yield "lm_head", self.lm_head.weight
 
-    def decode_step(self, tokens, cache, logits_out):
+    def decode_step(self, tokens, cache, logits_out, weights=None):
         """:meth:`forward_cached` at T = 1 for a :class:`DecodeSession`, on device state only:
         the logits of ``tokens`` (B, 1) at position ``cache.start`` go into ``logits_out``.  Every
         projection is one ``ops.linear_decode`` with the norm in its prologue and the SwiGLU /
-        residual in its epilogue; the session has advanced ``cache.start`` / ``cache.lens``."""
+        residual in its epilogue; the session has advanced ``cache.start`` / ``cache.lens``.
+        A projection named in ``weights`` (name -> ``ops.Fp8Weight``) streams that weight."""
         cfg = self.config
         B, Hq, Hkv, D = tokens.shape[0], cfg.n_heads, cfg.n_kv_heads, cfg.head_dim
         cos, sin = self.rope_cos, self.rope_sin
         x = F.embedding(tokens[:, 0], self.embed_tokens.weight)
+        ws = session_weights(self, weights)
         for i, layer in enumerate(self.layers):
             at, ff = layer.self_attn, layer.mlp
             ln1, ln2 = layer.input_layernorm, layer.post_attention_layernorm
-            qkv = ops.linear_decode(x, at.qkv_proj.weight, norm="rms", norm_weight=ln1.weight,
+            w_qkv, w_o, w_gu, w_dn = (at.qkv_proj.weight, at.o_proj.weight, ff.gate_up_proj.weight,
+                                      ff.down_proj.weight) if ws is None else ws[4 * i:4 * i + 4]
+            qkv = ops.linear_decode(x, w_qkv, norm="rms", norm_weight=ln1.weight,
                                     eps=ln1.eps).view(B, 1, Hq + 2 * Hkv, D)
             kc, vc = cache.layer(i)
             q = ops.kv_append(qkv[:, :, Hq:Hq + Hkv], qkv[:, :, Hq + Hkv:], kc, vc, cache.start,
                               q=qkv[:, :, :Hq], cos=cos, sin=sin)
             y = ops.attention_decode(q[:, 0], kc, vc, cache.lens)
-            x = ops.linear_decode(y.view(B, Hq * D), at.o_proj.weight, residual=x)
-            h = ops.linear_decode(x, ff.gate_up_proj.weight, norm="rms", norm_weight=ln2.weight, eps=ln2.eps,
+            x = ops.linear_decode(y.view(B, Hq * D), w_o, residual=x)
+            h = ops.linear_decode(x, w_gu, norm="rms", norm_weight=ln2.weight, eps=ln2.eps,
                                   act="swiglu")
-            x = ops.linear_decode(h, ff.down_proj.weight, residual=x)
-        ops.linear_decode(x, self.lm_head.weight, norm="rms", norm_weight=self.norm.weight, eps=self.norm.eps,
+            x = ops.linear_decode(h, w_dn, residual=x)
+        w_head = self.lm_head.weight if ws is None else ws[-1]
+        ops.linear_decode(x, w_head, norm="rms", norm_weight=self.norm.weight, eps=self.norm.eps,
                           out=logits_out)
 
 

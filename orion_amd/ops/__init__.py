@@ -20,6 +20,7 @@ import torch.nn.functional as F
 
 from . import reference as ref
 from ._ext import ext_available, load_ext
+from .fp8 import Fp8Weight, quantize_fp8
 # loaded here, before ``def linear`` below binds the name: the first import of a submodule
 # sets it as an attribute of the package, which later would replace the function
 from .linear import linear_hip
@@ -355,7 +356,8 @@ def kv_append(k_new, v_new, k_cache, v_cache, kv_lens, q=None, cos=None, sin=Non
 def linear_decode_eligible(x, weight):
     """Whether the skinny decode kernel (csrc/linear_decode.hip) takes this input on the HIP
     backend: bf16 GPU tensors, at most 16 rows of x with 16-byte aligned unit-stride rows,
-    K % 8 == 0, a contiguous weight."""
+    K % 8 == 0, a contiguous weight.  With an :class:`Fp8Weight`, whether the FP8 kernel
+    (csrc/linear_decode_fp8.hip) does: the same for bf16 x, with K % 16 == 0."""
     if not x.is_cuda or _BACKEND != "hip":
         return False
     from .decode import linear_decode_eligible as ok
@@ -387,15 +389,20 @@ def linear_decode(x, weight, bias=None, *, norm=None, norm_weight=None, norm_bia
     [gate; up] weight of 2F rows -> (..., F)), ``residual`` a distinct tensor of the output's
     shape.  On the GPU one weight-streaming launch when :func:`linear_decode_eligible` (at most 16
     rows), else the plain ops composed; ``out`` (rows, Nout) takes the result in place.
-    Inference only."""
+    ``weight`` may be an :class:`Fp8Weight`: an eligible input streams its bytes through the FP8
+    kernel, any other (the CPU, the torch backend, 17 or more rows) takes the path it would take
+    with a plain weight, on ``weight.dequant(x.dtype)``.  Inference only."""
     assert norm in (None, "layer", "rms") and act in (None, "gelu", "swiglu"), (norm, act)
     assert (norm is None) == (norm_weight is None), "norm_weight comes with a norm"
     from .decode import _no_grad
-    _no_grad(x, weight, bias, norm_weight, norm_bias, residual)
+    fp8 = isinstance(weight, Fp8Weight)
+    _no_grad(x, None if fp8 else weight, bias, norm_weight, norm_bias, residual)
     b = _gpu(x)
     if b == "hip" and linear_decode_eligible(x, weight):
         from .decode import linear_decode_hip
         return linear_decode_hip(x, weight, bias, norm, norm_weight, norm_bias, eps, act, residual, out)
+    if fp8:
+        weight = weight.dequant(x.dtype)
     if b is None:
         y = ref.linear_decode(x, weight, bias, norm, norm_weight, norm_bias, eps, act, residual)
     else:
@@ -493,7 +500,7 @@ __all__ = [
     "cross_entropy", "swiglu_mlp", "linear_residual_layer_norm", "mlp_residual_layer_norm",
     "linear_residual_rms_norm", "swiglu_residual_rms_norm",
     "linear_cross_entropy", "attention_decode", "kv_append", "linear_decode", "linear_decode_eligible",
-    "sample_tokens", "sample_tokens_eligible",
+    "sample_tokens", "sample_tokens_eligible", "Fp8Weight", "quantize_fp8",
 ]
 
 

@@ -1,7 +1,8 @@
-"""Generation-time ops over the HIP kernels of csrc/attn_decode.hip and csrc/linear_decode.hip:
-single-query attention against a key/value cache (split over keys, lengths read on the device),
-the cache append with optional RoPE, and the skinny (M <= 16) linear layer with a fused norm
-prologue and bias / activation / residual epilogue.  Inference only: there is no backward, and
+"""Generation-time ops over the HIP kernels of csrc/attn_decode.hip, csrc/linear_decode.hip and
+csrc/linear_decode_fp8.hip: single-query attention against a key/value cache (split over keys,
+lengths read on the device), the cache append with optional RoPE, and the skinny (M <= 16) linear
+layer with a fused norm prologue and bias / activation / residual epilogue, on a bf16 weight or
+an :class:`~orion_amd.ops.fp8.Fp8Weight`.  Inference only: there is no backward, and
 an input that requires grad while gradients are enabled is an error rather than a silently
 dropped graph."""
 from __future__ import annotations
@@ -11,6 +12,7 @@ import math
 import torch
 
 from ._ext import C
+from .fp8 import Fp8Weight
 
 
 def _no_grad(*tensors):
@@ -31,13 +33,19 @@ def _rows16(t):
 def linear_decode_eligible(x, weight):
     """Whether csrc/linear_decode.hip takes x (..., K) (at most 16 rows that flatten to a view with
     16-byte aligned, unit-stride rows) against weight (N, K): both bf16 on the GPU, K % 8 == 0,
-    weight contiguous."""
-    if not (x.is_cuda and weight.is_cuda and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16):
+    weight contiguous.  For an :class:`Fp8Weight`, whether csrc/linear_decode_fp8.hip does: the
+    same with K % 16 == 0."""
+    kmult = 8
+    if isinstance(weight, Fp8Weight):
+        kmult, weight = 16, weight.q
+    elif weight.dtype != torch.bfloat16:
+        return False
+    if not (x.is_cuda and weight.is_cuda and x.dtype == torch.bfloat16):
         return False
     if weight.dim() != 2 or x.dim() < 1 or x.shape[-1] != weight.shape[1] or not weight.is_contiguous():
         return False
     K = weight.shape[1]
-    if K < 8 or K % 8 or weight.data_ptr() % 16 or x.numel() == 0 or x.numel() // K > MAX_ROWS:
+    if K < kmult or K % kmult or weight.data_ptr() % 16 or x.numel() == 0 or x.numel() // K > MAX_ROWS:
         return False
     try:
         x2 = x.view(-1, K)
@@ -50,12 +58,16 @@ def linear_decode_hip(x, weight, bias=None, norm=None, norm_weight=None, norm_bi
                       residual=None, out=None):
     """One launch: act(norm(x) W^T + bias) + residual for x (..., K) of at most 16 rows -> (..., Nout);
     ``out`` (rows, Nout) receives the result in place (a static buffer of a captured step)."""
-    _no_grad(x, weight, bias, norm_weight, norm_bias, residual)
+    _no_grad(x, None if isinstance(weight, Fp8Weight) else weight, bias, norm_weight, norm_bias, residual)
     K = weight.shape[1]
     n_out = weight.shape[0] // 2 if act == "swiglu" else weight.shape[0]
     r2 = None if residual is None else residual.view(-1, n_out)
-    y = C().linear_decode(x.view(-1, K), weight, bias, NORMS[norm], norm_weight, norm_bias, float(eps), ACTS[act],
-                          r2, out)
+    if isinstance(weight, Fp8Weight):
+        y = C().linear_decode_fp8(x.view(-1, K), weight.q, weight.scale, bias, NORMS[norm], norm_weight, norm_bias,
+                                  float(eps), ACTS[act], r2, out)
+    else:
+        y = C().linear_decode(x.view(-1, K), weight, bias, NORMS[norm], norm_weight, norm_bias, float(eps),
+                              ACTS[act], r2, out)
     return y.view(*x.shape[:-1], n_out)
 
 

@@ -11,7 +11,9 @@ token, ``generate(use_cache=True)``) instead of re-running the whole prefix; ``-
 runs those tokens on the fused decode step and ``--kv_cache=graph`` replays that step from one
 captured HIP graph (``generate(use_cache="fused" / "graph")``).  ``--sampler=device`` (with
 ``fused`` or ``graph``) draws the tokens with the sampling kernel inside that step instead of stock
-torch ops between the steps (``generate(..., sampler="device")``).
+torch ops between the steps (``generate(..., sampler="device")``).  ``--decode_weights=fp8`` (with
+``fused`` or ``graph``) decodes from per-row FP8 (e4m3) copies of the projection weights, quantised
+once per sample (``generate(..., weights="fp8")``).
 """
 from __future__ import annotations
 
@@ -24,7 +26,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 DEFAULTS = dict(out_dir="out", start="\n", num_samples=10, max_new_tokens=500, temperature=0.8,
-                top_k=200, seed=1337, device="cuda", ckpt="ckpt.pt", kv_cache=False, sampler="torch")
+                top_k=200, seed=1337, device="cuda", ckpt="ckpt.pt", kv_cache=False, sampler="torch",
+                decode_weights="bf16")
 
 
 def main(argv=None):
@@ -67,9 +70,10 @@ def main(argv=None):
     kv = cfg["kv_cache"]
     with torch.no_grad():
         for _ in range(cfg["num_samples"]):
-            # generate() rejects a --kv_cache or --sampler it does not know
+            # generate() rejects a --kv_cache, --sampler or --decode_weights it does not know
             y = model.generate(x, cfg["max_new_tokens"], temperature=cfg["temperature"], top_k=cfg["top_k"],
-                               use_cache=kv if isinstance(kv, str) else bool(kv), sampler=cfg["sampler"])
+                               use_cache=kv if isinstance(kv, str) else bool(kv), sampler=cfg["sampler"],
+                               weights=cfg["decode_weights"])
             toks = y[0].tolist()
             print(decode(toks) if decode else toks)
             print("---------------")

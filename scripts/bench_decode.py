@@ -4,15 +4,17 @@ torch SDPA on the same cache view, at the GPT-2 and the Llama-GQA decode shapes;
 tokens/s of ``gpt2`` with and without the KV cache (prompt 64 + 256 new tokens at B 1 and 8, and
 a long-context point, prompt 768 at B 8) and on the fused decode step, eager (``fused``) and
 replayed from one captured HIP graph (``graph``) and with the tokens drawn inside that graph
-(``graph_device``: ``sampler="device"``), the arms alternating; (iii) the skinny decode
-linear (csrc/linear_decode.hip) at every projection shape of ``gpt2`` and of the Llama-2-7B layer
-at M = 1, 8, 16 beside the same call through ``F.linear`` with its separate norm / activation /
-residual launches; (iv) the sampling kernel (csrc/sample.hip) beside ``sample_logits`` (stock
+(``graph_device``: ``sampler="device"``) and from FP8 weights (``graph_device_fp8``: also
+``weights="fp8"``), the arms alternating; (iii) the skinny decode linear (csrc/linear_decode.hip)
+and its FP8-weight form (csrc/linear_decode_fp8.hip) at every projection shape of ``gpt2`` and of
+the Llama-2-7B layer at M = 1, 8, 16 beside the same call through ``F.linear`` with its separate
+norm / activation / residual launches; (iv) the sampling kernel (csrc/sample.hip) beside ``sample_logits`` (stock
 torch ops) on the same logits at B 1, 8, 16 and V 50,304 and 32,000, top-k 200 and none.
 
 The kernel timing rotates over enough distinct caches to exceed the 256 MB Infinity Cache, so
 every call streams its K and V from HBM; bytes/s counts the K + V actually read (one pass per
-KV head); the linear timing rotates over weights the same way and counts the weight bytes.
+KV head); the linear timing rotates over weights the same way (each arm over more than 512 MB of
+its own format) and counts the weight bytes (the FP8 arm's: one per element and four per row).
 Prints one JSON line per measurement.
 
 usage: python scripts/bench_decode.py [--kernel 0|1] [--linear 0|1] [--sample 0|1] [--generate 0|1] [--rounds N]
@@ -110,12 +112,18 @@ def bench_linear(model, name, N, K, norm, act, bias, residual, M, rounds):
     w_bytes = N * K * 2
     n_buf = max(2, math.ceil(512e6 / w_bytes))
     ws = [r(N, K) for _ in range(n_buf)]
+    q_bytes = N * K + 4 * N
+    n_q = max(2, math.ceil(512e6 / q_bytes))
+    qs = [ops.quantize_fp8(ws[i] if i < n_buf else r(N, K)) for i in range(n_q)]
     n_out = N // 2 if act == "swiglu" else N
     x, b, res = r(M, K), (r(N) if bias else None), (r(M, n_out) if residual else None)
     nw, nb = (r(K) if norm else None), (r(K) if norm == "layer" else None)
 
     def hip(i):
         return ops.linear_decode(x, ws[i % n_buf], b, norm=norm, norm_weight=nw, norm_bias=nb, act=act, residual=res)
+
+    def fp8(i):
+        return ops.linear_decode(x, qs[i % n_q], b, norm=norm, norm_weight=nw, norm_bias=nb, act=act, residual=res)
 
     def stock(i):
         h = x
@@ -132,17 +140,20 @@ def bench_linear(model, name, N, K, norm, act, bias, residual, M, rounds):
             y = F.silu(gate) * up
         return y if res is None else y + res
 
-    assert ops.linear_decode_eligible(x, ws[0])
+    assert ops.linear_decode_eligible(x, ws[0]) and ops.linear_decode_eligible(x, qs[0])
     err = (hip(0).float() - stock(0).float()).abs().max().item()
-    us = _time_us({"hip": hip, "f_linear": stock}, rounds)
+    us = _time_us({"hip": hip, "fp8": fp8, "f_linear": stock}, rounds)
     out = dict(bench="linear_decode", model=model, proj=name, M=M, N=N, K=K, norm=norm, act=act, bias=bias,
                residual=residual, w_mbytes=round(w_bytes / 1e6, 2), rotating_weights=n_buf,
+               fp8_w_mbytes=round(q_bytes / 1e6, 2), fp8_rotating_weights=n_q,
                max_abs_diff_vs_f_linear=round(err, 4), hbm_copy_TBs=HBM_COPY_TBS)
     for k, v in us.items():
         out[f"{k}_us"] = round(v, 2)
-        out[f"{k}_GBs"] = round(w_bytes / v / 1e3, 1)
+        out[f"{k}_GBs"] = round((q_bytes if k == "fp8" else w_bytes) / v / 1e3, 1)
     out["hip_over_copy_rate"] = round(out["hip_GBs"] / 1e3 / HBM_COPY_TBS, 3)
+    out["fp8_over_copy_rate"] = round(out["fp8_GBs"] / 1e3 / HBM_COPY_TBS, 3)
     out["speedup"] = round(us["f_linear"] / us["hip"], 2)
+    out["fp8_over_hip"] = round(us["hip"] / us["fp8"], 2)  # > 1: the FP8 kernel is faster than the bf16 one
     print(json.dumps(out), flush=True)
 
 
@@ -173,12 +184,13 @@ def bench_sample(B, V, top_k, rounds):
     print(json.dumps(res), flush=True)
 
 
-def bench_graph_steady(model, B, prompt_len, new_tokens):
-    """The graph arm without its capture: per-token time of the sampling loop on a captured
-    session, and of the replay alone (the rest is the sampling launches)."""
+def bench_graph_steady(model, B, prompt_len, new_tokens, weights="bf16"):
+    """The graph arm without its capture (and, with FP8 weights, without the quantisation):
+    per-token time of the sampling loop on a captured session, and of the replay alone (the rest
+    is the sampling launches)."""
     from orion_amd.models.generation import sample_logits
     prompt = torch.randint(0, 50257, (B, prompt_len), device="cuda")
-    sess = model.decode_session(B, prompt_len + new_tokens, graph=True)
+    sess = model.decode_session(B, prompt_len + new_tokens, graph=True, weights=weights)
     logits = sess.prefill(prompt)
     nxt = sample_logits(logits, 1.0, 200)
     sess.step(nxt)  # warm-up + capture
@@ -204,7 +216,8 @@ def bench_generate(B, prompt_len, new_tokens, rounds):
     model = build_gpt2("gpt2").to("cuda").to(torch.bfloat16).eval()
     prompt = torch.randint(0, 50257, (B, prompt_len), device="cuda")
     arms = {"cached": dict(use_cache=True), "uncached": dict(use_cache=False), "fused": dict(use_cache="fused"),
-            "graph": dict(use_cache="graph"), "graph_device": dict(use_cache="graph", sampler="device")}
+            "graph": dict(use_cache="graph"), "graph_device": dict(use_cache="graph", sampler="device"),
+            "graph_device_fp8": dict(use_cache="graph", sampler="device", weights="fp8")}
     for kw in arms.values():  # warm-up: every shape of every arm
         model.generate(prompt, new_tokens, top_k=200, **kw)
     torch.cuda.synchronize()
@@ -227,10 +240,35 @@ def bench_generate(B, prompt_len, new_tokens, rounds):
     res["fused_over_best_baseline"] = round(best / med["fused"], 2)
     res["graph_over_best_baseline"] = round(best / med["graph"], 2)
     res["graph_device_over_graph"] = round(med["graph"] / med["graph_device"], 2)
+    res["graph_device_fp8_over_graph_device"] = round(med["graph_device"] / med["graph_device_fp8"], 2)
     steady = bench_graph_steady(model, B, prompt_len, new_tokens)
     res["graph_steady_ms_per_token"] = round(steady["token"] * 1e3, 3)
     res["graph_replay_ms_per_token"] = round(steady["replay"] * 1e3, 3)
     res["graph_sampling_ms_per_token"] = round((steady["token"] - steady["replay"]) * 1e3, 3)
+    steady = bench_graph_steady(model, B, prompt_len, new_tokens, weights="fp8")
+    res["graph_fp8_replay_ms_per_token"] = round(steady["replay"] * 1e3, 3)
+    print(json.dumps(res), flush=True)
+
+
+def bench_weight_bytes():
+    """Bytes of projection weight a decode session holds, bf16 beside fp8: ``gpt2`` from real
+    sessions (with the relative logit error of the fp8 session's prefill against the unquantised
+    model, random init), the Llama-2-7B shape from its projection shapes alone."""
+    from orion_amd.models.llama import build_llama
+    torch.manual_seed(0)
+    model = build_gpt2("gpt2").to("cuda").to(torch.bfloat16).eval()
+    prompt = torch.randint(0, 50257, (8, 64), device="cuda")
+    s16, s8 = model.decode_session(8, 128), model.decode_session(8, 128, weights="fp8")
+    a, b = s16.prefill(prompt).float(), s8.prefill(prompt).float()
+    for tok in torch.randint(0, 50257, (16, 8, 1), device="cuda"):
+        a, b = s16.step(tok).float(), s8.step(tok).float()
+    res = dict(bench="decode_weight_bytes", gpt2_bf16_mbytes=round(s16.weight_bytes / 1e6, 1),
+               gpt2_fp8_mbytes=round(s8.weight_bytes / 1e6, 1),
+               gpt2_fp8_rel_logit_err_vs_bf16_random_init=round(((a - b).norm() / a.norm()).item(), 4))
+    with torch.device("meta"):
+        shapes = [tuple(w.shape) for _, w in build_llama("llama2-7b").decode_projections()]
+    res["llama2_7b_bf16_mbytes"] = round(sum(2 * n * k for n, k in shapes) / 1e6, 1)
+    res["llama2_7b_fp8_mbytes"] = round(sum(n * k + 4 * n for n, k in shapes) / 1e6, 1)
     print(json.dumps(res), flush=True)
 
 
@@ -260,6 +298,7 @@ def main():
                     for top_k in (200, None):
                         bench_sample(B, V, top_k, rounds=max(a.rounds, 5))
         if a.generate:
+            bench_weight_bytes()
             for B in (1, 8):
                 bench_generate(B, 64, 256, a.rounds)
             bench_generate(8, 768, 256, a.rounds)  # a long context: where re-running the prefix costs
