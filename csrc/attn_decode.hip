@@ -27,13 +27,13 @@
 // rounded once) and v (copied bit for bit) land in the cache, the rotated q in a contiguous
 // output.  Positions outside [0, Tmax) are skipped (their q rows are zero).
 #include "common.h"
+#include "attn_decode_lanes.h"
 #include "launchers.h"
 
 namespace orion {
 
 namespace {
 
-constexpr int DEC_NW = 4;  // waves per workgroup
 constexpr int DEC_U = 4;   // K (and V) loads in flight per wave and tile
 
 template <int D>
@@ -42,44 +42,6 @@ struct DecodeShape {
   static constexpr int KPW = 64 / LPK;               // keys per wave-wide load
   static constexpr int TILE = DEC_NW * DEC_U * KPW;  // keys per workgroup iteration
 };
-
-// 8 bf16 products summed in fp32: four v_dot2c_f32_bf16.  The pairs are taken by shufflevector
-// on the __bf16 vector: taking them as words of a u32x4 bit cast compiled to four dots of word 0.
-ORION_DEVICE float dot8_bf16(bf16x8 a, bf16x8 b) {
-  const bf16x8_mfma av = __builtin_bit_cast(bf16x8_mfma, a), bv = __builtin_bit_cast(bf16x8_mfma, b);
-  float s = 0.f;
-  s = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(av, av, 0, 1), __builtin_shufflevector(bv, bv, 0, 1),
-                                      s, false);
-  s = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(av, av, 2, 3), __builtin_shufflevector(bv, bv, 2, 3),
-                                      s, false);
-  s = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(av, av, 4, 5), __builtin_shufflevector(bv, bv, 4, 5),
-                                      s, false);
-  s = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(av, av, 6, 7), __builtin_shufflevector(bv, bv, 6, 7),
-                                      s, false);
-  return s;
-}
-
-// Sum over the aligned group of LPK (8 or 16) lanes that hold one key row, every lane getting
-// the total, on DPP moves (no LDS-pipe ds_bpermute in the key loop): quad_perm [1,0,3,2] and
-// [2,3,0,1] sum a quad; the quads' sums being uniform, row_half_mirror (lane i <- 7 - i) adds the
-// other quad of the 8 and row_mirror (i <- 15 - i) the other half of the 16-lane row.
-template <int CTRL>
-ORION_DEVICE float dpp_add(float v) {
-  const int x = __builtin_bit_cast(int, v);
-  return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(x, x, CTRL, 0xf, 0xf, false));
-}
-
-template <int LPK>
-ORION_DEVICE float key_lanes_sum(float v) {
-  static_assert(LPK == 8 || LPK == 16, "a key row spans 8 or 16 lanes");
-  v = dpp_add<0xB1>(v);   // quad_perm [1,0,3,2]
-  v = dpp_add<0x4E>(v);   // quad_perm [2,3,0,1]
-  v = dpp_add<0x141>(v);  // row_half_mirror
-  if constexpr (LPK == 16) v = dpp_add<0x140>(v);  // row_mirror
-  return v;
-}
-
-ORION_DEVICE float finite_or_zero(float m) { return m == -INFINITY ? 0.f : m; }
 
 }  // namespace
 
@@ -334,9 +296,8 @@ static int orion_attn_decode_tile(int D) { return D == 64 ? DecodeShape<64>::TIL
 
 // Splits chosen on the host from the caller's upper bound on the length (the cache view's
 // Tmax): enough workgroups for two per CU of the 256 when the length allows, each split a
-// whole number of key tiles.  Returns the split count and the keys per split.
-int orion_attn_decode_plan(int B, int Hkv, int Tmax, int D, int splits, int* chunk) {
-  const int tile = orion_attn_decode_tile(D);
+// whole number of key tiles of `tile` keys.  Returns the split count and the keys per split.
+int orion_attn_decode_split_plan(int tile, int B, int Hkv, int Tmax, int splits, int* chunk) {
   const int tiles = Tmax > 0 ? (Tmax + tile - 1) / tile : 1;
   if (splits <= 0) {
     const long groups = (long)B * Hkv;
@@ -352,6 +313,18 @@ int orion_attn_decode_plan(int B, int Hkv, int Tmax, int D, int splits, int* chu
   return splits;
 }
 
+int orion_attn_decode_plan(int B, int Hkv, int Tmax, int D, int splits, int* chunk) {
+  return orion_attn_decode_split_plan(orion_attn_decode_tile(D), B, Hkv, Tmax, splits, chunk);
+}
+
+// The merge of the splits' partials into bf16 o (B * Hq heads of D columns).
+int orion_attn_decode_combine(const float* ws_o, const float* ws_ml, void* o, int splits, int D, long heads,
+                              hipStream_t st) {
+  const long n = heads * D;
+  attn_decode_combine_kernel<<<(int)((n + 255) / 256), 256, 0, st>>>(ws_o, ws_ml, (bf16_t*)o, splits, D, heads);
+  return (int)hipGetLastError();
+}
+
 template <int D>
 static int launch_decode(const DecodeParams& p, hipStream_t st) {
   const int G = p.Hq / p.Hkv;
@@ -362,10 +335,7 @@ static int launch_decode(const DecodeParams& p, hipStream_t st) {
   else attn_decode_kernel<D, 1><<<grid, 256, 0, st>>>(p);
   int rc = (int)hipGetLastError();
   if (rc || p.splits == 1) return rc;
-  const long n = (long)p.B * p.Hq * D;
-  attn_decode_combine_kernel<<<(int)((n + 255) / 256), 256, 0, st>>>(p.ws_o, p.ws_ml, p.o, p.splits, D,
-                                                                     (long)p.B * p.Hq);
-  return (int)hipGetLastError();
+  return orion_attn_decode_combine(p.ws_o, p.ws_ml, p.o, p.splits, D, (long)p.B * p.Hq, st);
 }
 
 int orion_attn_decode(const DecodeParams& p, int D, hipStream_t st) {

@@ -1001,11 +1001,12 @@ void check_cache_inputs(const Tensor& k_cache, const Tensor& v_cache, const Tens
   TORCH_CHECK(k_cache.device() == v_cache.device() && k_cache.device() == kv_lens.device(), "device mismatch");
 }
 
-// q (B, Hq, D), caches (B, Tmax, Hkv, D), kv_lens (B,) int32 on the device -> o (B, Hq, D).
-// splits = 0: chosen from Tmax, the caller's host-side bound on the length (pass a cache view).
-Tensor attn_decode(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& kv_lens,
-                   double scale, int64_t splits) {
-  check_cache_inputs(k_cache, v_cache, kv_lens);
+// What attn_decode and attn_decode_fp8 share: the checks on q and splits, the split plan (`plan`: the
+// kernel's own) with its workspace (kept alive by ws_o / ws_ml), and every field of the parameter
+// block P but the scales.  The caller holds the device guard.  Returns o.
+template <class P, class Plan>
+Tensor attn_decode_args(P& p, Plan plan, const Tensor& q, const Tensor& k_cache, const Tensor& v_cache,
+                        const Tensor& kv_lens, double scale, int64_t splits, Tensor& ws_o, Tensor& ws_ml) {
   check_bf16(q, "q");
   TORCH_CHECK(q.dim() == 3 && q.size(0) == k_cache.size(0) && q.size(2) == k_cache.size(3),
               "q must be (B, Hq, D) matching the cache");
@@ -1013,13 +1014,10 @@ Tensor attn_decode(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache
   TORCH_CHECK(q.device() == k_cache.device(), "device mismatch");
   TORCH_CHECK(splits >= 0 && splits <= 1024, "splits must be in [0, 1024]");
   check_rows16(q, "q");
-  c10::hip::HIPGuardMasqueradingAsCUDA g(q.device());
   const int D = q.size(2);
-  orion::DecodeParams p{};
   p.B = q.size(0); p.Hq = q.size(1); p.Hkv = k_cache.size(2); p.Tmax = k_cache.size(1);
-  p.splits = orion_attn_decode_plan(p.B, p.Hkv, p.Tmax, D, (int)splits, &p.chunk);
+  p.splits = plan(p.B, p.Hkv, p.Tmax, D, (int)splits, &p.chunk);
   auto o = at::empty({p.B, p.Hq, D}, q.options());
-  Tensor ws_o, ws_ml;
   if (p.splits > 1) {
     ws_o = at::empty({p.B, p.Hq, p.splits, D}, q.options().dtype(at::kFloat));
     ws_ml = at::empty({p.B, p.Hq, p.splits, 2}, q.options().dtype(at::kFloat));
@@ -1033,17 +1031,29 @@ Tensor attn_decode(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache
   p.o = (unsigned short*)o.data_ptr();
   p.kv_lens = kv_lens.data_ptr<int>();
   p.scale_log2 = (float)(scale * LOG2E);
-  check_launch(orion_attn_decode(p, D, cur_stream()), "attn_decode");
   return o;
 }
 
-// k_new / v_new (B, T, Hkv, D) -> cache rows kv_lens[b] + t (positions >= Tmax are skipped); with
-// tables k is rotated on the way, and q (B, T, Hq, D) comes back rotated and contiguous (an
-// empty tensor without q).  kv_lens is not changed.
-Tensor kv_append(const Tensor& k_new, const Tensor& v_new, Tensor k_cache, Tensor v_cache, const Tensor& kv_lens,
-                 const c10::optional<Tensor>& q, const c10::optional<Tensor>& cosv,
-                 const c10::optional<Tensor>& sinv) {
+// q (B, Hq, D), caches (B, Tmax, Hkv, D), kv_lens (B,) int32 on the device -> o (B, Hq, D).
+// splits = 0: chosen from Tmax, the caller's host-side bound on the length (pass a cache view).
+Tensor attn_decode(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& kv_lens,
+                   double scale, int64_t splits) {
   check_cache_inputs(k_cache, v_cache, kv_lens);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(q.device());
+  orion::DecodeParams p{};
+  Tensor ws_o, ws_ml;
+  Tensor o = attn_decode_args(p, orion_attn_decode_plan, q, k_cache, v_cache, kv_lens, scale, splits, ws_o, ws_ml);
+  check_launch(orion_attn_decode(p, (int)q.size(2), cur_stream()), "attn_decode");
+  return o;
+}
+
+// What kv_append and kv_append_fp8 share: every check past the cache's own, and every field of the
+// parameter block P but the scales, the lengths and the caches' element type.  Returns the rotated q's
+// buffer (an empty tensor without q).
+template <class P>
+Tensor kv_append_args(P& p, const Tensor& k_new, const Tensor& v_new, const Tensor& k_cache, const Tensor& v_cache,
+                      const c10::optional<Tensor>& q, const c10::optional<Tensor>& cosv,
+                      const c10::optional<Tensor>& sinv) {
   check_bf16(k_new, "k_new"); check_bf16(v_new, "v_new");
   TORCH_CHECK(k_new.dim() == 4 && k_new.sizes() == v_new.sizes() && k_new.size(0) == k_cache.size(0) &&
                   k_new.size(2) == k_cache.size(2) && k_new.size(3) == k_cache.size(3),
@@ -1053,8 +1063,6 @@ Tensor kv_append(const Tensor& k_new, const Tensor& v_new, Tensor k_cache, Tenso
   const bool has_q = given(q), has_rope = given(cosv);
   TORCH_CHECK(has_rope == given(sinv), "kv_append: cos and sin come together");
   TORCH_CHECK(!has_q || has_rope, "kv_append: q is only taken for rotation (pass cos / sin)");
-  c10::hip::HIPGuardMasqueradingAsCUDA g(k_new.device());
-  orion::AppendParams p{};
   p.B = k_new.size(0); p.T = k_new.size(1); p.Hkv = k_new.size(2); p.D = k_new.size(3);
   p.Tmax = k_cache.size(1);
   TORCH_CHECK((int64_t)p.B * p.T < (1LL << 31) - p.Tmax, "kv_append: too many tokens");
@@ -1084,8 +1092,80 @@ Tensor kv_append(const Tensor& k_new, const Tensor& v_new, Tensor k_cache, Tenso
   set_view(p.v_new, p.vn_sb, p.vn_st, p.vn_sh, v_new);
   set_view(p.k_cache, p.kc_sb, p.kc_st, p.kc_sh, k_cache);
   set_view(p.v_cache, p.vc_sb, p.vc_st, p.vc_sh, v_cache);
+  return q_out;
+}
+
+// k_new / v_new (B, T, Hkv, D) -> cache rows kv_lens[b] + t (positions >= Tmax are skipped); with
+// tables k is rotated on the way, and q (B, T, Hq, D) comes back rotated and contiguous (an
+// empty tensor without q).  kv_lens is not changed.
+Tensor kv_append(const Tensor& k_new, const Tensor& v_new, Tensor k_cache, Tensor v_cache, const Tensor& kv_lens,
+                 const c10::optional<Tensor>& q, const c10::optional<Tensor>& cosv,
+                 const c10::optional<Tensor>& sinv) {
+  check_cache_inputs(k_cache, v_cache, kv_lens);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(k_new.device());
+  orion::AppendParams p{};
+  Tensor q_out = kv_append_args(p, k_new, v_new, k_cache, v_cache, q, cosv, sinv);
   p.kv_lens = kv_lens.data_ptr<int>();
   check_launch(orion_kv_append(p, cur_stream()), "kv_append");
+  return q_out;
+}
+
+// ------------------------------------------------------------------ FP8 key/value cache (csrc/attn_decode_fp8.hip)
+// e4m3 bytes (B, Tmax, Hkv, D) with unit stride on D and 8-byte aligned rows; fp32 scales
+// (B, Hkv, Tmax) with unit stride on the tokens
+void check_fp8_cache_inputs(const Tensor& k_cache, const Tensor& v_cache, const Tensor& k_scale,
+                            const Tensor& v_scale, const Tensor& kv_lens) {
+  TORCH_CHECK(k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes(), "k_cache / v_cache must be (B, Tmax, Hkv, D)");
+  const int64_t B = k_cache.size(0), Tmax = k_cache.size(1), Hkv = k_cache.size(2), D = k_cache.size(3);
+  TORCH_CHECK(D == 64 || D == 128, "head dim must be 64 or 128, got ", D);
+  TORCH_CHECK(B > 0 && Hkv > 0 && Tmax < (1 << 30), "empty or oversized cache");
+  for (const Tensor* t : {&k_cache, &v_cache}) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat8_e4m3fn,
+                "an FP8 cache must be Float8_e4m3fn (OCP e4m3) on the GPU, got ", t->scalar_type());
+    for (int64_t i = 0; i < 3; ++i) TORCH_CHECK(t->stride(i) % 8 == 0, "an FP8 cache needs 8-byte aligned rows");
+    TORCH_CHECK(t->stride(3) == 1 && (uintptr_t)t->data_ptr() % 8 == 0,
+                "an FP8 cache needs unit stride on the head dim and an 8-byte aligned base");
+  }
+  for (const Tensor* t : {&k_scale, &v_scale})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->dim() == 3 && t->size(0) == B &&
+                    t->size(1) == Hkv && t->size(2) == Tmax && (Tmax == 1 || t->stride(2) == 1),
+                "k_scale / v_scale must be float32 (B, Hkv, Tmax) with unit stride on the tokens");
+  TORCH_CHECK(kv_lens.is_cuda() && kv_lens.scalar_type() == at::kInt && kv_lens.dim() == 1 &&
+                  kv_lens.is_contiguous() && kv_lens.size(0) == B,
+              "kv_lens must be a contiguous int32 (B,) tensor on the device");
+  TORCH_CHECK(k_cache.device() == v_cache.device() && k_cache.device() == kv_lens.device() &&
+                  k_cache.device() == k_scale.device() && k_cache.device() == v_scale.device(),
+              "device mismatch");
+}
+
+// attn_decode on an FP8 cache: q (B, Hq, D) bf16 -> o (B, Hq, D) bf16.
+Tensor attn_decode_fp8(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& k_scale,
+                       const Tensor& v_scale, const Tensor& kv_lens, double scale, int64_t splits) {
+  check_fp8_cache_inputs(k_cache, v_cache, k_scale, v_scale, kv_lens);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(q.device());
+  orion::DecodeFp8Params p{};
+  Tensor ws_o, ws_ml;
+  Tensor o = attn_decode_args(p, orion_attn_decode_fp8_plan, q, k_cache, v_cache, kv_lens, scale, splits, ws_o,
+                              ws_ml);
+  p.k_scale = k_scale.data_ptr<float>(); p.ks_sb = k_scale.stride(0); p.ks_sh = k_scale.stride(1);
+  p.v_scale = v_scale.data_ptr<float>(); p.vs_sb = v_scale.stride(0); p.vs_sh = v_scale.stride(1);
+  check_launch(orion_attn_decode_fp8(p, (int)q.size(2), cur_stream()), "attn_decode_fp8");
+  return o;
+}
+
+// kv_append into an FP8 cache: each head row of k_new (rotated when tables are given) and v_new is
+// quantised by its own amax; bytes and scales land at kv_lens[b] + t.  Returns the rotated bf16 q.
+Tensor kv_append_fp8(const Tensor& k_new, const Tensor& v_new, Tensor k_cache, Tensor v_cache, Tensor k_scale,
+                     Tensor v_scale, const Tensor& kv_lens, const c10::optional<Tensor>& q,
+                     const c10::optional<Tensor>& cosv, const c10::optional<Tensor>& sinv) {
+  check_fp8_cache_inputs(k_cache, v_cache, k_scale, v_scale, kv_lens);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(k_new.device());
+  orion::AppendFp8Params p{};
+  Tensor q_out = kv_append_args(p, k_new, v_new, k_cache, v_cache, q, cosv, sinv);
+  p.k_scale = k_scale.data_ptr<float>(); p.ks_sb = k_scale.stride(0); p.ks_sh = k_scale.stride(1);
+  p.v_scale = v_scale.data_ptr<float>(); p.vs_sb = v_scale.stride(0); p.vs_sh = v_scale.stride(1);
+  p.kv_lens = kv_lens.data_ptr<int>();
+  check_launch(orion_kv_append_fp8(p, cur_stream()), "kv_append_fp8");
   return q_out;
 }
 
@@ -1308,6 +1388,8 @@ TORCH_LIBRARY(orion_amd, m) {
   m.def("attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, bool causal, float scale, Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, int flags=0, Tensor(d!)? bias_grad=None, Tensor? rope_cos=None, Tensor? rope_sin=None, int rope_pos0=0) -> ()");
   m.def("attn_decode(Tensor q, Tensor k_cache, Tensor v_cache, Tensor kv_lens, float scale, int splits=0) -> Tensor");
   m.def("kv_append(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor kv_lens, Tensor? q=None, Tensor? cos=None, Tensor? sin=None) -> Tensor");
+  m.def("attn_decode_fp8(Tensor q, Tensor k_cache, Tensor v_cache, Tensor k_scale, Tensor v_scale, Tensor kv_lens, float scale, int splits=0) -> Tensor");
+  m.def("kv_append_fp8(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor(c!) k_scale, Tensor(d!) v_scale, Tensor kv_lens, Tensor? q=None, Tensor? cos=None, Tensor? sin=None) -> Tensor");
   m.def("linear_decode(Tensor x, Tensor w, Tensor? bias, int norm, Tensor? norm_w, Tensor? norm_b, float eps, int act, Tensor? residual, Tensor(a!)? out=None) -> Tensor");
   m.def("linear_decode_fp8(Tensor x, Tensor wq, Tensor w_scale, Tensor? bias, int norm, Tensor? norm_w, Tensor? norm_b, float eps, int act, Tensor? residual, Tensor(a!)? out=None) -> Tensor");
   m.def("sample_tokens(Tensor logits, Tensor params, Tensor? u, Tensor? seed, Tensor? positions, Tensor(a!)? out=None, Tensor(b!)? history=None, Tensor(c!)? u_out=None) -> Tensor");
@@ -1350,6 +1432,8 @@ TORCH_LIBRARY_IMPL(orion_amd, CUDA, m) {
   m.impl("attn_bwd", &attn_bwd);
   m.impl("attn_decode", &attn_decode);
   m.impl("kv_append", &kv_append);
+  m.impl("attn_decode_fp8", &attn_decode_fp8);
+  m.impl("kv_append_fp8", &kv_append_fp8);
   m.impl("linear_decode", &linear_decode);
   m.impl("linear_decode_fp8", &linear_decode_fp8);
   m.impl("sample_tokens", &sample_tokens);

@@ -8,6 +8,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "attn_decode_fp8_params.h"
 #include "attn_decode_params.h"
 #include "attn_plan.h"
 #include "linear_decode_fp8_params.h"
@@ -110,10 +111,18 @@ int orion_lmhead_bwd_prep(const void* X, long ldx, int Cdim, long N, const int64
                           const float* invz, const float* inv_n, const float* g, float* srow, void* Xs,
                           int transposed, hipStream_t st);
 
-// attn_decode.hip, linear_decode.hip, linear_decode_fp8.hip, sample.hip: generation (negative: a field of p failed its check)
+// attn_decode.hip, attn_decode_fp8.hip, linear_decode.hip, linear_decode_fp8.hip, sample.hip: generation
+// (negative: a field of p failed its check)
+int orion_attn_decode_split_plan(int tile, int B, int Hkv, int Tmax, int splits, int* chunk);  // key tiles of `tile`
 int orion_attn_decode_plan(int B, int Hkv, int Tmax, int D, int splits, int* chunk);
 int orion_attn_decode(const orion::DecodeParams& p, int D, hipStream_t st);
+int orion_attn_decode_combine(const float* ws_o, const float* ws_ml, void* o, int splits, int D, long heads,
+                              hipStream_t st);
 int orion_kv_append(const orion::AppendParams& p, hipStream_t st);
+int orion_attn_decode_fp8_tile(int D);  // keys per workgroup iteration of the FP8 kernel
+int orion_attn_decode_fp8_plan(int B, int Hkv, int Tmax, int D, int splits, int* chunk);
+int orion_attn_decode_fp8(const orion::DecodeFp8Params& p, int D, hipStream_t st);
+int orion_kv_append_fp8(const orion::AppendFp8Params& p, hipStream_t st);
 int orion_linear_decode(const orion::LinearDecodeParams& p, hipStream_t st);
 int orion_linear_decode_fp8(const orion::LinearDecodeFp8Params& p, hipStream_t st);  // -1 also K % 16
 int orion_sample_tokens(const orion::SampleParams& p, hipStream_t st);

@@ -28,6 +28,7 @@
 //   * K % 16 == 0, so a 16-element fragment is inside or outside as a whole.  Nothing is read
 //     beyond row M - 1, weight row N - 1, scale[N - 1] or element K - 1.
 #include "common.h"
+#include "fp8_cvt.h"
 #include "launchers.h"
 #include "linear_decode_mfma.h"
 
@@ -40,16 +41,6 @@ constexpr int LQ_NW_WIDE = 8, LQ_U_WIDE = 4;  // plain projections with K >= LQ_
 constexpr int LQ_NW = 4;                      // the others: two blocks, one with a prologue
 constexpr int lq_u(int norm) { return norm == LD_NORM_NONE ? 2 : 1; }
 constexpr int LQ_K_WIDE = 64 * LQ_NW_WIDE * LQ_U_WIDE;  // one full round of the wide form
-
-// 8 e4m3 bytes (two words, ascending k) -> 8 bf16, exact
-ORION_DEVICE bf16x8 lq_cvt8(unsigned w0, unsigned w1) {
-  u32x4 r;
-  r[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, false));
-  r[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, true));
-  r[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, false));
-  r[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, true));
-  return __builtin_bit_cast(bf16x8, r);
-}
 
 template <int NORM, int NB, int U>
 struct LqStage {
@@ -195,7 +186,7 @@ __global__ __launch_bounds__(64 * NW) void linear_decode_fp8_kernel(const Linear
         }
 #pragma unroll
         for (int h = 0; h < NB; ++h)
-          acc[h] = ld_mfma(a, lq_cvt8(cur.w[h][u][2 * i], cur.w[h][u][2 * i + 1]), acc[h]);
+          acc[h] = ld_mfma(a, fp8x8_to_bf16(cur.w[h][u][2 * i], cur.w[h][u][2 * i + 1]), acc[h]);
       }
     }
     cur = nxt;

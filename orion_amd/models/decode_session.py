@@ -46,13 +46,25 @@ class DecodeSession:
     model's parameters are not modified and the embedding tables stay as they are (GPT-2's tied
     ``wte`` is quantised as the head only); activations, the cache, attention and sampling do
     not change.  With the default ``"bf16"``, ``qweights`` is None, ``weight_bytes`` counts the
-    model's own projection weights and the models are called exactly as without the keyword."""
+    model's own projection weights and the models are called exactly as without the keyword.
 
-    def __init__(self, model, batch, max_len=None, graph=False, sampler="torch", weights="bf16"):
+    ``kv="fp8"`` makes the cache a :class:`KVCache` with ``kv_dtype="fp8"``: the append quantises
+    each head row to e4m3 bytes with one fp32 scale (csrc/attn_decode_fp8.hip) and the decode
+    attention streams those bytes, (D + 4) / 2D of the bf16 cache's; ``cache_bytes`` is what the
+    cache holds.  The step keeps its launches (the two cache ops change kernels), so a captured
+    step stays one linear chain.  A prefill of more than one token attends the stored values of
+    each layer dequantised to a transient (``KVCache.dense_layer``), so a chunked prompt and the
+    decode steps see the same keys and values; the transient is one layer's k and v in the
+    activation dtype at a time.  With the default ``"bf16"`` the cache is built as without the
+    keyword."""
+
+    def __init__(self, model, batch, max_len=None, graph=False, sampler="torch", weights="bf16", kv="bf16"):
         if sampler not in ("torch", "device"):
             raise ValueError(f"sampler must be 'torch' or 'device', got {sampler!r}")
         if weights not in ("bf16", "fp8"):
             raise ValueError(f"weights must be 'bf16' or 'fp8', got {weights!r}")
+        if kv not in ("bf16", "fp8"):
+            raise ValueError(f"kv must be 'bf16' or 'fp8', got {kv!r}")
         cfg = model.config
         self.model = model
         self.batch = int(batch)
@@ -83,7 +95,9 @@ class DecodeSession:
                     raise ValueError(f"DecodeSession(graph=True): {name} {tuple(pw.shape)} {kind[0]} is not "
                                      f"eligible for ops.linear_decode (bf16 on the HIP backend, {kind[1]}, "
                                      "contiguous weight), and a library GEMM must not be captured")
-        self.cache = model.new_cache(self.batch, max_len)  # at most the model's context limit
+        self.kv = kv
+        self.cache = model.new_cache(self.batch, max_len, kv_dtype=kv)  # at most the model's context limit
+        self.cache_bytes = self.cache.nbytes
         self.max_len = self.cache.max_len
         self.tokens = torch.zeros(self.batch, 1, dtype=torch.long, device=w.device)
         self.logits = torch.zeros(self.batch, cfg.vocab_size, dtype=w.dtype, device=w.device)

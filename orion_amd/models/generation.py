@@ -39,16 +39,17 @@ def sample_logits(logits, temperature=1.0, top_k=None):
 class Generation:
     """``generate`` and ``decode_session`` of a model with a :class:`KVCache`."""
 
-    def decode_session(self, batch, max_len=None, graph=False, sampler="torch", weights="bf16"):
+    def decode_session(self, batch, max_len=None, graph=False, sampler="torch", weights="bf16", kv="bf16"):
         """A :class:`DecodeSession` for this model: the fused decode step, captured when ``graph``;
-        ``sampler="device"`` draws the tokens with ``ops.sample_tokens`` inside that step and
-        ``weights="fp8"`` decodes from per-row e4m3 copies of the projection weights."""
+        ``sampler="device"`` draws the tokens with ``ops.sample_tokens`` inside that step,
+        ``weights="fp8"`` decodes from per-row e4m3 copies of the projection weights and
+        ``kv="fp8"`` keeps the key/value cache as e4m3 bytes with one scale per (token, KV head)."""
         from .decode_session import DecodeSession
-        return DecodeSession(self, batch, max_len, graph=graph, sampler=sampler, weights=weights)
+        return DecodeSession(self, batch, max_len, graph=graph, sampler=sampler, weights=weights, kv=kv)
 
     @torch.no_grad()
     def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, use_cache=False, sampler="torch",
-                 weights="bf16"):
+                 weights="bf16", kv="bf16"):
         """nanoGPT's sampling loop.  ``use_cache=True`` keeps every layer's keys / values
         (:class:`KVCache`): the prompt is prefilled once and each new token costs one single-token
         forward.  Tokens beyond the context limit (``block_size`` / ``max_seq_len``) take the
@@ -60,7 +61,10 @@ class Generation:
         default generator) instead of stock torch ops between the steps, and ``weights="fp8"``
         makes the session quantise the projection weights once (``ops.quantize_fp8``) and run the
         prompt and every cached token on them.  The sliding-window loop beyond the context limit
-        keeps using the model's own (unquantised) weights, as it keeps clear of the session."""
+        keeps using the model's own (unquantised) weights, as it keeps clear of the session.
+        ``kv="fp8"`` (with ``use_cache`` True, ``"fused"`` or ``"graph"``) keeps the cache as e4m3
+        bytes with one fp32 scale per (token, KV head): about half the cache's memory and bytes per
+        step; the sliding-window loop has no cache and does not change."""
         fused = isinstance(use_cache, str)
         if fused and use_cache not in ("fused", "graph"):
             raise ValueError(f"use_cache must be False, True, 'fused' or 'graph', got {use_cache!r}")
@@ -74,16 +78,21 @@ class Generation:
         if weights == "fp8" and not fused:
             raise ValueError("weights='fp8' decodes through the fused decode step: use_cache must be 'fused' "
                              f"or 'graph', got {use_cache!r}")
+        if kv not in ("bf16", "fp8"):
+            raise ValueError(f"kv must be 'bf16' or 'fp8', got {kv!r}")
+        if kv == "fp8" and not use_cache:
+            raise ValueError("kv='fp8' is the key/value cache's format: use_cache must be True, 'fused' or "
+                             f"'graph', got {use_cache!r}")
         limit = self.context_len
         B, T = idx.shape
         if use_cache and max_new_tokens > 0 and T < limit:
             n = min(max_new_tokens, limit - T + 1)  # the n-th token is drawn from position limit - 1's logits
             if fused:
                 sess = self.decode_session(B, T + n - 1, graph=use_cache == "graph", sampler=sampler,
-                                           weights=weights)
+                                           weights=weights, kv=kv)
                 idx = sess.generate(idx, n, temperature, top_k)
             else:
-                cache = self.new_cache(B, T + n - 1)
+                cache = self.new_cache(B, T + n - 1, kv_dtype=kv)
                 logits = self.forward_cached(idx, cache)
                 for step in range(n):
                     nxt = sample_logits(logits, temperature, top_k)

@@ -207,12 +207,13 @@ class GPT(nn.Module, Generation):
     def context_len(self):
         return self.config.block_size
 
-    def new_cache(self, batch, max_len=None):
-        """An empty :class:`KVCache` for this model on its device (``max_len`` <= block_size)."""
+    def new_cache(self, batch, max_len=None, kv_dtype="bf16"):
+        """An empty :class:`KVCache` for this model on its device (``max_len`` <= block_size);
+        ``kv_dtype="fp8"`` stores e4m3 bytes with one scale per (token, head)."""
         cfg = self.config
         w = self.lm_head.weight
         return KVCache(cfg.n_layer, batch, min(max_len or cfg.block_size, cfg.block_size), cfg.n_head,
-                       cfg.head_dim, device=w.device, dtype=w.dtype)
+                       cfg.head_dim, device=w.device, dtype=w.dtype, kv_dtype=kv_dtype)
 
     @torch.no_grad()
     def forward_cached(self, idx, cache, weights=None):
@@ -222,7 +223,9 @@ class GPT(nn.Module, Generation):
         ops throughout: the training-time fused residual sites have no place at M = B.
         ``weights`` maps names of :meth:`decode_projections` to ``ops.Fp8Weight``: such a
         projection runs on its dequantised weight, one transient at a time (the embedding tables
-        stay the model's)."""
+        stay the model's).  An FP8 ``cache`` (``new_cache(kv_dtype="fp8")``) takes the
+        appended keys / values quantised with their scales, and a T > 1 call attends the stored
+        values dequantised (``cache.dense_layer``): what the decode steps will read."""
         B, T = idx.shape
         cfg, tr = self.config, self.transformer
         assert cache.pos + T <= cfg.block_size, f"sequence {cache.pos + T} > block_size {cfg.block_size}"
@@ -238,12 +241,15 @@ class GPT(nn.Module, Generation):
                 if ws is None else ws[4 * i:4 * i + 4]
             qkv = ops.linear(h, dense(w_qkv, h.dtype), at.c_attn.bias).view(B, T, 3, H, D)
             kc, vc = cache.layer(i)
-            ops.kv_append(qkv[:, :, 1], qkv[:, :, 2], kc, vc, cache.start)
+            ks, vs = cache.layer_scales(i)  # (None, None) unless the cache is FP8
+            ops.kv_append(qkv[:, :, 1], qkv[:, :, 2], kc, vc, cache.start, k_scale=ks, v_scale=vs)
             end = pos + T  # the host's bound of the length: the key split is planned from it
             if T == 1:
-                y = ops.attention_decode(qkv[:, 0, 0], kc[:, :end], vc[:, :end], cache.lens)
-            else:
-                y = ops.attention(qkv[:, :, 0], kc[:, :end], vc[:, :end], causal=True)
+                if ks is not None:
+                    ks, vs = ks[:, :, :end], vs[:, :, :end]
+                y = ops.attention_decode(qkv[:, 0, 0], kc[:, :end], vc[:, :end], cache.lens, k_scale=ks, v_scale=vs)
+            else:  # an FP8 cache is attended as stored (dequantised): what the decode steps will see
+                y = ops.attention(qkv[:, :, 0], *cache.dense_layer(i, end, h.dtype), causal=True)
             a = ops.linear(y.reshape(B, T, H * D), dense(w_o, h.dtype), at.c_proj.bias)
             x, h = ops.add_layer_norm(x, a, block.ln_2.weight, block.ln_2.bias)
             m = ops.mlp(h, dense(w_fc, h.dtype), ml.c_fc.bias, dense(w_pr, h.dtype), ml.c_proj.bias)
@@ -278,9 +284,10 @@ class GPT(nn.Module, Generation):
             qkv = ops.linear_decode(x, w_qkv, at.c_attn.bias, norm="layer", norm_weight=blk.ln_1.weight,
                                     norm_bias=blk.ln_1.bias).view(B, 1, 3, H, D)
             kc, vc = cache.layer(i)
-            ops.kv_append(qkv[:, :, 1], qkv[:, :, 2], kc, vc, cache.start)
+            ks, vs = cache.layer_scales(i)
+            ops.kv_append(qkv[:, :, 1], qkv[:, :, 2], kc, vc, cache.start, k_scale=ks, v_scale=vs)
             # the whole cache view: the key split is planned from max_len once and never changes
-            y = ops.attention_decode(qkv[:, 0, 0], kc, vc, cache.lens)
+            y = ops.attention_decode(qkv[:, 0, 0], kc, vc, cache.lens, k_scale=ks, v_scale=vs)
             x = ops.linear_decode(y.view(B, H * D), w_o, at.c_proj.bias, residual=x)
             h = ops.linear_decode(x, w_fc, ml.c_fc.bias, norm="layer", norm_weight=blk.ln_2.weight,
                                   norm_bias=blk.ln_2.bias, act="gelu")

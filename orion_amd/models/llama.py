@@ -174,12 +174,13 @@ class Llama(nn.Module, Generation):
     def context_len(self):
         return self.config.max_seq_len
 
-    def new_cache(self, batch, max_len=None):
-        """An empty :class:`KVCache` for this model on its device (``max_len`` <= max_seq_len)."""
+    def new_cache(self, batch, max_len=None, kv_dtype="bf16"):
+        """An empty :class:`KVCache` for this model on its device (``max_len`` <= max_seq_len);
+        ``kv_dtype="fp8"`` stores e4m3 bytes with one scale per (token, KV head)."""
         cfg = self.config
         w = self.lm_head.weight
         return KVCache(cfg.n_layers, batch, min(max_len or cfg.max_seq_len, cfg.max_seq_len), cfg.n_kv_heads,
-                       cfg.head_dim, device=w.device, dtype=w.dtype)
+                       cfg.head_dim, device=w.device, dtype=w.dtype, kv_dtype=kv_dtype)
 
     @torch.no_grad()
     def forward_cached(self, idx, cache, weights=None):
@@ -189,7 +190,9 @@ class Llama(nn.Module, Generation):
         Plain ops throughout: the training-time fused residual sites have no place at M = B.
         ``weights`` maps names of :meth:`decode_projections` to ``ops.Fp8Weight``: such a
         projection runs on its dequantised weight, one transient at a time (the embedding table
-        stays the model's)."""
+        stays the model's).  An FP8 ``cache`` (``new_cache(kv_dtype="fp8")``) takes the
+        appended keys / values quantised with their scales, and a T > 1 call attends the stored
+        values dequantised (``cache.dense_layer``): what the decode steps will read."""
         B, T = idx.shape
         cfg = self.config
         assert cache.pos + T <= cfg.max_seq_len
@@ -207,12 +210,15 @@ class Llama(nn.Module, Generation):
                                       ff.down_proj.weight) if ws is None else ws[4 * i:4 * i + 4]
             qkv = ops.linear(h, dense(w_qkv, h.dtype)).view(B, T, Hq + 2 * Hkv, D)
             kc, vc = cache.layer(i)
+            ks, vs = cache.layer_scales(i)  # (None, None) unless the cache is FP8
             q = ops.kv_append(qkv[:, :, Hq:Hq + Hkv], qkv[:, :, Hq + Hkv:], kc, vc, cache.start,
-                              q=qkv[:, :, :Hq], cos=cos, sin=sin)
+                              q=qkv[:, :, :Hq], cos=cos, sin=sin, k_scale=ks, v_scale=vs)
             if T == 1:
-                y = ops.attention_decode(q[:, 0], kc[:, :end], vc[:, :end], cache.lens)
-            else:
-                y = ops.attention(q, kc[:, :end], vc[:, :end], causal=True)
+                if ks is not None:
+                    ks, vs = ks[:, :, :end], vs[:, :, :end]
+                y = ops.attention_decode(q[:, 0], kc[:, :end], vc[:, :end], cache.lens, k_scale=ks, v_scale=vs)
+            else:  # an FP8 cache is attended as stored (dequantised): what the decode steps will see
+                y = ops.attention(q, *cache.dense_layer(i, end, h.dtype), causal=True)
             a = ops.linear(y.reshape(B, T, Hq * D), dense(w_o, h.dtype))
             x, h = ops.add_rms_norm(x, a, pln.weight, pln.eps)
             m = ops.swiglu_mlp(h, dense(w_gu, h.dtype), dense(w_dn, h.dtype))
@@ -249,9 +255,10 @@ class Llama(nn.Module, Generation):
             qkv = ops.linear_decode(x, w_qkv, norm="rms", norm_weight=ln1.weight,
                                     eps=ln1.eps).view(B, 1, Hq + 2 * Hkv, D)
             kc, vc = cache.layer(i)
+            ks, vs = cache.layer_scales(i)
             q = ops.kv_append(qkv[:, :, Hq:Hq + Hkv], qkv[:, :, Hq + Hkv:], kc, vc, cache.start,
-                              q=qkv[:, :, :Hq], cos=cos, sin=sin)
-            y = ops.attention_decode(q[:, 0], kc, vc, cache.lens)
+                              q=qkv[:, :, :Hq], cos=cos, sin=sin, k_scale=ks, v_scale=vs)
+            y = ops.attention_decode(q[:, 0], kc, vc, cache.lens, k_scale=ks, v_scale=vs)
             x = ops.linear_decode(y.view(B, Hq * D), w_o, residual=x)
             h = ops.linear_decode(x, w_gu, norm="rms", norm_weight=ln2.weight, eps=ln2.eps,
                                   act="swiglu")

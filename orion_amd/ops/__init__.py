@@ -20,7 +20,7 @@ import torch.nn.functional as F
 
 from . import reference as ref
 from ._ext import ext_available, load_ext
-from .fp8 import Fp8Weight, quantize_fp8
+from .fp8 import Fp8Weight, quantize_fp8, quantize_kv_fp8
 # loaded here, before ``def linear`` below binds the name: the first import of a submodule
 # sets it as an attribute of the package, which later would replace the function
 from .linear import linear_hip
@@ -325,32 +325,44 @@ def attention(q, k, v, causal=True):
 
 
 # --------------------------------------------------------------------------- generation
-def attention_decode(q, k_cache, v_cache, kv_lens, scale=None, splits=0):
+def attention_decode(q, k_cache, v_cache, kv_lens, scale=None, splits=0, k_scale=None, v_scale=None):
     """One query per row against a key/value cache: q (B, Hq, D), caches (B, Tmax, Hkv, D), kv_lens
     (B,) int32 -> (B, Hq, D).  Row b attends keys [0, min(kv_lens[b], Tmax)); what lies beyond is
     never used (stale NaN included) and an empty row is zeros.  The GPU kernel reads the lengths
     on the device and splits the keys over ``splits`` workgroups per KV head (0: chosen from
-    Tmax, so pass the cache cut at the host's bound of the length); inference only."""
+    Tmax, so pass the cache cut at the host's bound of the length); inference only.
+    ``float8_e4m3fn`` caches (:class:`KVCache` with ``kv_dtype="fp8"``) come with their fp32
+    scales ``k_scale`` / ``v_scale`` (B, Hkv, Tmax), value = scale * byte, and run
+    csrc/attn_decode_fp8.hip; bf16 caches refuse scales."""
+    fp8 = ref.cache_is_fp8(k_cache, v_cache, k_scale, v_scale)
     b = _gpu(q)
     if b == "hip":
-        from .decode import attention_decode_hip
+        from .decode import attention_decode_fp8_hip, attention_decode_hip
+        if fp8:
+            return attention_decode_fp8_hip(q, k_cache, v_cache, k_scale, v_scale, kv_lens, scale, splits)
         return attention_decode_hip(q, k_cache, v_cache, kv_lens, scale, splits)
     if b == "torch":
         from .decode import attention_decode_torch
-        return attention_decode_torch(q, k_cache, v_cache, kv_lens, scale)
-    return ref.attention_decode(q, k_cache, v_cache, kv_lens, scale)
+        return attention_decode_torch(q, k_cache, v_cache, kv_lens, scale, k_scale, v_scale)
+    return ref.attention_decode(q, k_cache, v_cache, kv_lens, scale, k_scale, v_scale)
 
 
-def kv_append(k_new, v_new, k_cache, v_cache, kv_lens, q=None, cos=None, sin=None):
+def kv_append(k_new, v_new, k_cache, v_cache, kv_lens, q=None, cos=None, sin=None, k_scale=None, v_scale=None):
     """Write k_new / v_new (B, T, Hkv, D) into the caches at positions kv_lens[b] + t (skipping
     positions >= Tmax; kv_lens itself is unchanged).  With fp32 tables (``ref.rope_tables``) k is
     rotated at its position on the way in, and with q (B, T, Hq, D) the rotated q is returned as a
-    new contiguous tensor (else None).  One launch on the GPU; inference only."""
+    new contiguous tensor (else None).  One launch on the GPU; inference only.  Into
+    ``float8_e4m3fn`` caches every head row is quantised by :func:`quantize_kv_fp8` (k from its
+    fp32 rotated values) and its scale stored in ``k_scale`` / ``v_scale`` (B, Hkv, Tmax); bf16
+    caches refuse scales."""
+    fp8 = ref.cache_is_fp8(k_cache, v_cache, k_scale, v_scale)
     b = _gpu(k_new)
     if b == "hip":
-        from .decode import kv_append_hip
+        from .decode import kv_append_fp8_hip, kv_append_hip
+        if fp8:
+            return kv_append_fp8_hip(k_new, v_new, k_cache, v_cache, k_scale, v_scale, kv_lens, q, cos, sin)
         return kv_append_hip(k_new, v_new, k_cache, v_cache, kv_lens, q, cos, sin)
-    return ref.kv_append(k_new, v_new, k_cache, v_cache, kv_lens, q, cos, sin)
+    return ref.kv_append(k_new, v_new, k_cache, v_cache, kv_lens, q, cos, sin, k_scale, v_scale)
 
 
 def linear_decode_eligible(x, weight):
@@ -500,7 +512,7 @@ __all__ = [
     "cross_entropy", "swiglu_mlp", "linear_residual_layer_norm", "mlp_residual_layer_norm",
     "linear_residual_rms_norm", "swiglu_residual_rms_norm",
     "linear_cross_entropy", "attention_decode", "kv_append", "linear_decode", "linear_decode_eligible",
-    "sample_tokens", "sample_tokens_eligible", "Fp8Weight", "quantize_fp8",
+    "sample_tokens", "sample_tokens_eligible", "Fp8Weight", "quantize_fp8", "quantize_kv_fp8",
 ]
 
 

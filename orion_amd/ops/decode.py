@@ -1,6 +1,7 @@
-"""Generation-time ops over the HIP kernels of csrc/attn_decode.hip, csrc/linear_decode.hip and
-csrc/linear_decode_fp8.hip: single-query attention against a key/value cache (split over keys,
-lengths read on the device), the cache append with optional RoPE, and the skinny (M <= 16) linear
+"""Generation-time ops over the HIP kernels of csrc/attn_decode.hip, csrc/attn_decode_fp8.hip,
+csrc/linear_decode.hip and csrc/linear_decode_fp8.hip: single-query attention against a bf16 or
+FP8 key/value cache (split over keys, lengths read on the device), the cache append with optional
+RoPE (quantising into an FP8 cache), and the skinny (M <= 16) linear
 layer with a fused norm prologue and bias / activation / residual epilogue, on a bf16 weight or
 an :class:`~orion_amd.ops.fp8.Fp8Weight`.  Inference only: there is no backward, and
 an input that requires grad while gradients are enabled is an error rather than a silently
@@ -12,7 +13,7 @@ import math
 import torch
 
 from ._ext import C
-from .fp8 import Fp8Weight
+from .fp8 import Fp8Weight, dequantize_kv_fp8
 
 
 def _no_grad(*tensors):
@@ -88,6 +89,27 @@ def kv_append_hip(k_new, v_new, k_cache, v_cache, kv_lens, q=None, cos=None, sin
     return q_rot if q is not None else None
 
 
+def attention_decode_fp8_tile(D):
+    """Keys per workgroup iteration of csrc/attn_decode_fp8.hip (its ``DecodeFp8Shape<D>::TILE``:
+    4 waves x 4 loads x 64 / (D / 8) keys per wave-wide load); a split is a whole number of them."""
+    return 4 * 4 * (64 // (D // 8))
+
+
+def attention_decode_fp8_hip(q, k_cache, v_cache, k_scale, v_scale, kv_lens, scale=None, splits=0):
+    """:func:`attention_decode_hip` on ``float8_e4m3fn`` caches with fp32 scales (B, Hkv, Tmax)."""
+    _no_grad(q, k_cache, v_cache, k_scale, v_scale)
+    scale = 1.0 / math.sqrt(q.shape[-1]) if scale is None else float(scale)
+    return C().attn_decode_fp8(q, k_cache, v_cache, k_scale, v_scale, kv_lens, scale, int(splits))
+
+
+def kv_append_fp8_hip(k_new, v_new, k_cache, v_cache, k_scale, v_scale, kv_lens, q=None, cos=None, sin=None):
+    """One launch: :func:`kv_append_hip` into ``float8_e4m3fn`` caches, every head row quantised by
+    its own amax (``ops.fp8.quantize_kv_fp8``) and its scale stored beside the bytes."""
+    _no_grad(k_new, v_new, k_cache, v_cache, k_scale, v_scale, q)
+    q_rot = C().kv_append_fp8(k_new, v_new, k_cache, v_cache, k_scale, v_scale, kv_lens, q, cos, sin)
+    return q_rot if q is not None else None
+
+
 def sample_tokens_eligible(logits):
     """Whether csrc/sample.hip takes these logits: (B, V) bf16 on the GPU with unit stride on V
     (any row stride, any alignment of the rows)."""
@@ -124,9 +146,11 @@ def sample_tokens_hip(logits, params, u=None, seed=None, positions=None, out=Non
     return C().sample_tokens(logits, params, u, seed, positions, out, history, u_out).view(-1, 1)
 
 
-def attention_decode_torch(q, k_cache, v_cache, kv_lens, scale=None):
-    """Stock PyTorch: SDPA on each row's valid slice (reads the lengths on the host)."""
+def attention_decode_torch(q, k_cache, v_cache, kv_lens, scale=None, k_scale=None, v_scale=None):
+    """Stock PyTorch: SDPA on each row's valid slice (reads the lengths on the host); the slice of
+    an FP8 cache is dequantised to ``q.dtype`` first."""
     _no_grad(q, k_cache, v_cache)
+    fp8 = k_scale is not None
     B, Hq, D = q.shape
     Tmax, Hkv = k_cache.shape[1], k_cache.shape[2]
     rep = Hq // Hkv
@@ -135,8 +159,11 @@ def attention_decode_torch(q, k_cache, v_cache, kv_lens, scale=None):
         n = max(0, min(int(n), Tmax))
         if n == 0:
             continue
-        k = k_cache[b, :n].transpose(0, 1)  # (Hkv, n, D)
-        v = v_cache[b, :n].transpose(0, 1)
+        k, v = k_cache[b, :n], v_cache[b, :n]
+        if fp8:
+            k = dequantize_kv_fp8(k, k_scale[b, :, :n], q.dtype)
+            v = dequantize_kv_fp8(v, v_scale[b, :, :n], q.dtype)
+        k, v = k.transpose(0, 1), v.transpose(0, 1)  # (Hkv, n, D)
         if rep > 1:
             k, v = k.repeat_interleave(rep, 0), v.repeat_interleave(rep, 0)
         out[b] = torch.nn.functional.scaled_dot_product_attention(

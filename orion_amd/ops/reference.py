@@ -98,10 +98,32 @@ def attention(q, k, v, causal=True, scale=None):
     return o.to(q.dtype)
 
 
-def attention_decode(q, k_cache, v_cache, kv_lens, scale=None):
+def cache_is_fp8(k_cache, v_cache, k_scale, v_scale):
+    """Whether the caches are FP8: then both scales (B, Hkv, Tmax) are required, else refused."""
+    fp8 = k_cache.dtype == torch.float8_e4m3fn
+    if fp8 != (v_cache.dtype == torch.float8_e4m3fn):
+        raise ValueError(f"k_cache and v_cache must share a dtype, got {k_cache.dtype} and {v_cache.dtype}")
+    if fp8 and (k_scale is None or v_scale is None):
+        raise ValueError("float8_e4m3fn caches need k_scale and v_scale (B, Hkv, Tmax)")
+    if not fp8 and (k_scale is not None or v_scale is not None):
+        raise ValueError(f"k_scale / v_scale go with float8_e4m3fn caches, not {k_cache.dtype}")
+    if fp8:
+        want = (k_cache.shape[0], k_cache.shape[2], k_cache.shape[1])
+        if tuple(k_scale.shape) != want or tuple(v_scale.shape) != want:
+            raise ValueError(f"k_scale / v_scale must be (B, Hkv, Tmax) = {want}, got {tuple(k_scale.shape)} and "
+                             f"{tuple(v_scale.shape)}")
+    return fp8
+
+
+def attention_decode(q, k_cache, v_cache, kv_lens, scale=None, k_scale=None, v_scale=None):
     """One query per row against a key/value cache: q (B, Hq, D), caches (B, Tmax, Hkv, D),
     kv_lens (B,) -> (B, Hq, D).  Row b attends keys [0, min(kv_lens[b], Tmax)); positions beyond
-    are never read (they may hold anything), and a row of length 0 is zeros."""
+    are never read (they may hold anything), and a row of length 0 is zeros.  FP8 caches
+    (``float8_e4m3fn`` with fp32 scales (B, Hkv, Tmax)) are dequantised to fp32, exactly, first."""
+    if cache_is_fp8(k_cache, v_cache, k_scale, v_scale):
+        from .fp8 import dequantize_kv_fp8
+        return attention_decode(q, dequantize_kv_fp8(k_cache, k_scale), dequantize_kv_fp8(v_cache, v_scale),
+                                kv_lens, scale)
     B, Hq, D = q.shape
     Tmax, Hkv = k_cache.shape[1], k_cache.shape[2]
     rep = Hq // Hkv
@@ -118,11 +140,14 @@ def attention_decode(q, k_cache, v_cache, kv_lens, scale=None):
     return out.to(q.dtype)
 
 
-def kv_append(k_new, v_new, k_cache, v_cache, kv_lens, q=None, cos=None, sin=None):
+def kv_append(k_new, v_new, k_cache, v_cache, kv_lens, q=None, cos=None, sin=None, k_scale=None, v_scale=None):
     """Write k_new / v_new (B, T, Hkv, D) into the caches (B, Tmax, Hkv, D) at positions
     kv_lens[b] + t; positions >= Tmax are skipped.  With tables k is rotated at its position
     (fp32, rounded once) and, given q (B, T, Hq, D), the rotated q is returned as a new tensor
-    (rows of skipped positions are zero).  kv_lens is not changed."""
+    (rows of skipped positions are zero).  kv_lens is not changed.  FP8 caches take each head row
+    through ``ops.fp8.quantize_kv_fp8`` (k from its fp32 rotated values): bytes into the caches,
+    scales into k_scale / v_scale (B, Hkv, Tmax)."""
+    fp8 = cache_is_fp8(k_cache, v_cache, k_scale, v_scale)
     B, T = k_new.shape[:2]
     Tmax = k_cache.shape[1]
     assert q is None or cos is not None, "q is only taken for rotation (pass cos / sin)"
@@ -134,9 +159,16 @@ def kv_append(k_new, v_new, k_cache, v_cache, kv_lens, q=None, cos=None, sin=Non
             continue
         kb = k_new[b:b + 1, :n]
         if cos is not None:
-            kb = rope(kb, cos[p0:p0 + n], sin[p0:p0 + n])
+            kb = rope(kb.float() if fp8 else kb, cos[p0:p0 + n], sin[p0:p0 + n])  # fp32 in, fp32 out
             if q is not None:
                 q_rot[b:b + 1, :n] = rope(q[b:b + 1, :n], cos[p0:p0 + n], sin[p0:p0 + n])
+        if fp8:
+            from .fp8 import quantize_kv_fp8
+            for cache, sc, x in ((k_cache, k_scale, kb[0]), (v_cache, v_scale, v_new[b, :n])):
+                bytes_, s = quantize_kv_fp8(x)  # (n, Hkv, D), (n, Hkv)
+                cache[b, p0:p0 + n] = bytes_
+                sc[b, :, p0:p0 + n] = s.t()
+            continue
         k_cache[b, p0:p0 + n] = kb[0].to(k_cache.dtype)
         v_cache[b, p0:p0 + n] = v_new[b, :n].to(v_cache.dtype)
     return q_rot

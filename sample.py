@@ -13,7 +13,9 @@ captured HIP graph (``generate(use_cache="fused" / "graph")``).  ``--sampler=dev
 ``fused`` or ``graph``) draws the tokens with the sampling kernel inside that step instead of stock
 torch ops between the steps (``generate(..., sampler="device")``).  ``--decode_weights=fp8`` (with
 ``fused`` or ``graph``) decodes from per-row FP8 (e4m3) copies of the projection weights, quantised
-once per sample (``generate(..., weights="fp8")``).
+once per sample (``generate(..., weights="fp8")``).  ``--decode_kv=fp8`` (with any ``--kv_cache``)
+keeps the key/value cache as FP8 (e4m3) bytes with one scale per token and head
+(``generate(..., kv="fp8")``): about half the cache's memory.
 """
 from __future__ import annotations
 
@@ -27,7 +29,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 DEFAULTS = dict(out_dir="out", start="\n", num_samples=10, max_new_tokens=500, temperature=0.8,
                 top_k=200, seed=1337, device="cuda", ckpt="ckpt.pt", kv_cache=False, sampler="torch",
-                decode_weights="bf16")
+                decode_weights="bf16", decode_kv="bf16")
 
 
 def main(argv=None):
@@ -70,10 +72,10 @@ def main(argv=None):
     kv = cfg["kv_cache"]
     with torch.no_grad():
         for _ in range(cfg["num_samples"]):
-            # generate() rejects a --kv_cache, --sampler or --decode_weights it does not know
+            # generate() rejects a --kv_cache, --sampler, --decode_weights or --decode_kv it does not know
             y = model.generate(x, cfg["max_new_tokens"], temperature=cfg["temperature"], top_k=cfg["top_k"],
                                use_cache=kv if isinstance(kv, str) else bool(kv), sampler=cfg["sampler"],
-                               weights=cfg["decode_weights"])
+                               weights=cfg["decode_weights"], kv=cfg["decode_kv"])
             toks = y[0].tolist()
             print(decode(toks) if decode else toks)
             print("---------------")

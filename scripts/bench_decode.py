@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
 """Generation benchmark: (i) the split-KV decode attention kernel (csrc/attn_decode.hip) beside
-torch SDPA on the same cache view, at the GPT-2 and the Llama-GQA decode shapes; (ii) generated
+torch SDPA on the same cache view and beside its FP8-cache form (csrc/attn_decode_fp8.hip) on the
+quantised caches, at the GPT-2, the Llama-GQA and the Llama-2-7B MHA decode shapes; (ii) generated
 tokens/s of ``gpt2`` with and without the KV cache (prompt 64 + 256 new tokens at B 1 and 8, and
 a long-context point, prompt 768 at B 8) and on the fused decode step, eager (``fused``) and
 replayed from one captured HIP graph (``graph``) and with the tokens drawn inside that graph
 (``graph_device``: ``sampler="device"``) and from FP8 weights (``graph_device_fp8``: also
-``weights="fp8"``), the arms alternating; (iii) the skinny decode linear (csrc/linear_decode.hip)
+``weights="fp8"``) or an FP8 key/value cache (``graph_device_kvfp8``: ``kv="fp8"``), the arms
+alternating; (iii) the skinny decode linear (csrc/linear_decode.hip)
 and its FP8-weight form (csrc/linear_decode_fp8.hip) at every projection shape of ``gpt2`` and of
 the Llama-2-7B layer at M = 1, 8, 16 beside the same call through ``F.linear`` with its separate
 norm / activation / residual launches; (iv) the sampling kernel (csrc/sample.hip) beside ``sample_logits`` (stock
@@ -13,11 +15,13 @@ torch ops) on the same logits at B 1, 8, 16 and V 50,304 and 32,000, top-k 200 a
 
 The kernel timing rotates over enough distinct caches to exceed the 256 MB Infinity Cache, so
 every call streams its K and V from HBM; bytes/s counts the K + V actually read (one pass per
-KV head); the linear timing rotates over weights the same way (each arm over more than 512 MB of
-its own format) and counts the weight bytes (the FP8 arm's: one per element and four per row).
+KV head; the FP8 arm's own bytes: one per element and four per (token, head) scale); the linear
+timing rotates over weights the same way (each arm over more than 512 MB of its own format) and
+counts the weight bytes (the FP8 arm's: one per element and four per row).
 Prints one JSON line per measurement.
 
-usage: python scripts/bench_decode.py [--kernel 0|1] [--linear 0|1] [--sample 0|1] [--generate 0|1] [--rounds N]
+usage: python scripts/bench_decode.py [--shapes a,b] [--kernel 0|1] [--linear 0|1] [--sample 0|1] [--generate 0|1]
+                                      [--rounds N]
 """
 import argparse
 import json
@@ -34,7 +38,8 @@ from orion_amd import ops  # noqa: E402
 from orion_amd.models.gpt2 import build_gpt2  # noqa: E402
 
 HBM_COPY_TBS = 6.29  # measured float4 copy rate of the MI355X (8.0 TB/s spec)
-SHAPES = {"gpt2": dict(B=8, Hq=12, Hkv=12, D=64, T=1024), "llama-gqa": dict(B=8, Hq=32, Hkv=8, D=128, T=4096)}
+SHAPES = {"gpt2": dict(B=8, Hq=12, Hkv=12, D=64, T=1024), "llama-gqa": dict(B=8, Hq=32, Hkv=8, D=128, T=4096),
+          "llama2-7b-mha": dict(B=16, Hq=32, Hkv=32, D=128, T=4096)}
 
 
 def _time_us(fns, rounds, calls=40):
@@ -65,8 +70,15 @@ def _time_us(fns, rounds, calls=40):
 def bench_kernel(name, B, Hq, Hkv, D, T, rounds):
     g = torch.Generator(device="cuda").manual_seed(0)
     kv_bytes = 2 * B * T * Hkv * D * 2
+    q_bytes = 2 * B * T * Hkv * (D + 4)
     n_buf = max(2, math.ceil(512e6 / kv_bytes))
+    n_q = max(2, math.ceil(512e6 / q_bytes))
     caches = [torch.randn(2, B, T, Hkv, D, device="cuda", generator=g).to(torch.bfloat16) for _ in range(n_buf)]
+    qcaches = []  # (bytes (2, B, T, Hkv, D), scales (2, B, Hkv, T)) of the same or further caches
+    for i in range(n_q):
+        src = caches[i] if i < n_buf else torch.randn(2, B, T, Hkv, D, device="cuda", generator=g).to(torch.bfloat16)
+        qb, qs = ops.quantize_kv_fp8(src)
+        qcaches.append((qb, qs.transpose(2, 3).contiguous()))
     q = torch.randn(B, Hq, D, device="cuda", generator=g).to(torch.bfloat16)
     lens = torch.full((B,), T, dtype=torch.int32, device="cuda")
     sdpa = torch.nn.functional.scaled_dot_product_attention
@@ -76,18 +88,26 @@ def bench_kernel(name, B, Hq, Hkv, D, T, rounds):
         c = caches[i % n_buf]
         return ops.attention_decode(q, c[0], c[1], lens)
 
+    def fp8(i):
+        c, sc = qcaches[i % n_q]
+        return ops.attention_decode(q, c[0], c[1], lens, k_scale=sc[0], v_scale=sc[1])
+
     def torch_sdpa(i):
         c = caches[i % n_buf]
         return sdpa(q4, c[0].transpose(1, 2), c[1].transpose(1, 2), enable_gqa=Hq != Hkv)
 
     err = (hip(0).float() - torch_sdpa(0)[:, :, 0].float()).abs().max().item()
-    us = _time_us({"hip": hip, "sdpa": torch_sdpa}, rounds)
+    err8 = (fp8(0).float() - hip(0).float()).abs().max().item()  # the quantisation of cache 0
+    us = _time_us({"hip": hip, "fp8": fp8, "sdpa": torch_sdpa}, rounds)
     res = dict(bench="decode_kernel", shape=name, B=B, Hq=Hq, Hkv=Hkv, D=D, len=T, kv_mbytes=round(kv_bytes / 1e6, 1),
-               rotating_caches=n_buf, max_abs_diff_vs_sdpa=round(err, 5), hbm_copy_TBs=HBM_COPY_TBS)
+               rotating_caches=n_buf, fp8_kv_mbytes=round(q_bytes / 1e6, 1), fp8_rotating_caches=n_q,
+               max_abs_diff_vs_sdpa=round(err, 5), fp8_max_abs_diff_vs_hip=round(err8, 5), hbm_copy_TBs=HBM_COPY_TBS)
     for k, v in us.items():
         res[f"{k}_us"] = round(v, 2)
-        res[f"{k}_TBs"] = round(kv_bytes / v / 1e6, 3)
+        res[f"{k}_TBs"] = round((q_bytes if k == "fp8" else kv_bytes) / v / 1e6, 3)
     res["hip_over_copy_rate"] = round(res["hip_TBs"] / HBM_COPY_TBS, 3)
+    res["fp8_over_copy_rate"] = round(res["fp8_TBs"] / HBM_COPY_TBS, 3)
+    res["fp8_over_hip"] = round(us["hip"] / us["fp8"], 2)  # > 1: the FP8 kernel is faster than the bf16 one
     print(json.dumps(res), flush=True)
 
 
@@ -217,7 +237,8 @@ def bench_generate(B, prompt_len, new_tokens, rounds):
     prompt = torch.randint(0, 50257, (B, prompt_len), device="cuda")
     arms = {"cached": dict(use_cache=True), "uncached": dict(use_cache=False), "fused": dict(use_cache="fused"),
             "graph": dict(use_cache="graph"), "graph_device": dict(use_cache="graph", sampler="device"),
-            "graph_device_fp8": dict(use_cache="graph", sampler="device", weights="fp8")}
+            "graph_device_fp8": dict(use_cache="graph", sampler="device", weights="fp8"),
+            "graph_device_kvfp8": dict(use_cache="graph", sampler="device", kv="fp8")}
     for kw in arms.values():  # warm-up: every shape of every arm
         model.generate(prompt, new_tokens, top_k=200, **kw)
     torch.cuda.synchronize()
@@ -241,6 +262,7 @@ def bench_generate(B, prompt_len, new_tokens, rounds):
     res["graph_over_best_baseline"] = round(best / med["graph"], 2)
     res["graph_device_over_graph"] = round(med["graph"] / med["graph_device"], 2)
     res["graph_device_fp8_over_graph_device"] = round(med["graph_device"] / med["graph_device_fp8"], 2)
+    res["graph_device_kvfp8_over_graph_device"] = round(med["graph_device"] / med["graph_device_kvfp8"], 2)
     steady = bench_graph_steady(model, B, prompt_len, new_tokens)
     res["graph_steady_ms_per_token"] = round(steady["token"] * 1e3, 3)
     res["graph_replay_ms_per_token"] = round(steady["replay"] * 1e3, 3)
@@ -279,14 +301,15 @@ def main():
     ap.add_argument("--sample", type=int, default=1)
     ap.add_argument("--generate", type=int, default=1)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--shapes", default=",".join(SHAPES), help="decode-kernel shapes, comma-separated")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_decode.py needs a GPU")
     ops.load_ext(required=True)
     with torch.no_grad():
         if a.kernel:
-            for name, s in SHAPES.items():
-                bench_kernel(name, rounds=max(a.rounds, 5) * 2, **s)
+            for name in a.shapes.split(","):
+                bench_kernel(name, rounds=max(a.rounds, 5) * 2, **SHAPES[name])
         if a.linear:
             for model, shapes in LINEAR_SHAPES.items():
                 for shape in shapes:
