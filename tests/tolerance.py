@@ -35,6 +35,31 @@ def within_bf16_budget(name, got, ref32, base_bf16, factor=FACTOR, floor=FLOOR):
     return e, b
 
 
+def slice_errs(t, ref32, dim=0):
+    """e_i = ||t_i - ref_i||_2 / (rms(ref32) sqrt(n_i)) for every index i along ``dim``: each
+    slice's rms error in units of the WHOLE reference's rms (a near-zero slice does not inflate
+    it).  A 1-D tensor has slices of one element."""
+    r = ref32.double()
+    d = (t.double() - r).pow(2)
+    if d.dim() > 1:
+        d = d.movedim(dim, 0).flatten(1).mean(1)
+    return d.sqrt() / (r.pow(2).mean().sqrt() + 1e-300)
+
+
+def within_bf16_budget_slices(name, got, ref32, base, dim=0, factor=FACTOR, floor=FLOOR):
+    """The budget above per slice along ``dim`` (per row of an activation, per element of a
+    column sum): max_i e_i(got) <= factor max_i e_i(base) + floor, e_i as in ``slice_errs``.
+    The whole-tensor budget cannot see one wrong row among thousands, the typical failure of a
+    row loop; this one can.  Returns (worst slice error, baseline's worst slice error)."""
+    assert got.shape == ref32.shape == base.shape, (name, got.shape, ref32.shape, base.shape)
+    eg = slice_errs(got, ref32, dim)
+    e, b = eg.max().item(), slice_errs(base, ref32, dim).max().item()
+    assert e <= factor * b + floor, (f"{name}: slice {int(eg.argmax())} along dim {dim} has error {e:.3e} "
+                                     f"(in units of the reference's rms), over {factor} x the baseline's "
+                                     f"worst slice {b:.3e} + {floor:.0e}")
+    return e, b
+
+
 def check_all(names, gots, refs, bases, factor=FACTOR, floor=FLOOR):
     """``within_bf16_budget`` over parallel sequences (outputs and gradients)."""
     out = {}
