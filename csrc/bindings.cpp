@@ -1047,6 +1047,42 @@ Tensor attn_decode(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache
   return o;
 }
 
+// q (B, Tq, Hq, D), Tq <= 16, against the caches with a causal tail -> o (B, Tq, Hq, D): query t of row b
+// attends keys [0, clamp(kv_lens[b] - Tq + 1 + t, 0, min(kv_lens[b], Tmax))).  The split plan is attn_decode's.
+Tensor attn_decode_multi(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& kv_lens,
+                         double scale, int64_t splits) {
+  check_cache_inputs(k_cache, v_cache, kv_lens);
+  check_bf16(q, "q");
+  TORCH_CHECK(q.dim() == 4 && q.size(0) == k_cache.size(0) && q.size(3) == k_cache.size(3),
+              "q must be (B, Tq, Hq, D) matching the cache");
+  TORCH_CHECK(q.size(1) >= 1 && q.size(1) <= 16, "Tq must be in [1, 16], got ", q.size(1));
+  TORCH_CHECK(q.size(2) > 0 && q.size(2) % k_cache.size(2) == 0, "Hq must be a multiple of Hkv");
+  TORCH_CHECK(q.device() == k_cache.device(), "device mismatch");
+  TORCH_CHECK(splits >= 0 && splits <= 1024, "splits must be in [0, 1024]");
+  check_rows16(q, "q");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(q.device());
+  orion::DecodeMultiParams p{};
+  const int D = q.size(3);
+  p.B = q.size(0); p.Tq = q.size(1); p.Hq = q.size(2); p.Hkv = k_cache.size(2); p.Tmax = k_cache.size(1);
+  p.splits = orion_attn_decode_plan(p.B, p.Hkv, p.Tmax, D, (int)splits, &p.chunk);
+  auto o = at::empty({p.B, p.Tq, p.Hq, D}, q.options());
+  Tensor ws_o, ws_ml;
+  if (p.splits > 1) {
+    ws_o = at::empty({p.B, p.Tq, p.Hq, p.splits, D}, q.options().dtype(at::kFloat));
+    ws_ml = at::empty({p.B, p.Tq, p.Hq, p.splits, 2}, q.options().dtype(at::kFloat));
+    p.ws_o = ws_o.data_ptr<float>();
+    p.ws_ml = ws_ml.data_ptr<float>();
+  }
+  set_view(p.q, p.q_sb, p.q_st, p.q_sh, q);
+  set_view(p.k, p.k_sb, p.k_st, p.k_sh, k_cache);
+  set_view(p.v, p.v_sb, p.v_st, p.v_sh, v_cache);
+  p.o = (unsigned short*)o.data_ptr();
+  p.kv_lens = kv_lens.data_ptr<int>();
+  p.scale_log2 = (float)(scale * LOG2E);
+  check_launch(orion_attn_decode_multi(p, D, cur_stream()), "attn_decode_multi");
+  return o;
+}
+
 // What kv_append and kv_append_fp8 share: every check past the cache's own, and every field of the
 // parameter block P but the scales, the lengths and the caches' element type.  Returns the rotated q's
 // buffer (an empty tensor without q).
@@ -1282,14 +1318,21 @@ Tensor linear_decode_fp8(const Tensor& x, const Tensor& wq, const Tensor& w_scal
 // the device holds the fp32 bits of T and top_k; u (B,) fp32 is given, or comes from Philox with
 // the int64 `seed` (1,) as key and (positions[b], b, 0, 0) as counter.  The token goes to `out`
 // (B,) or (B, 1) int64 and, with `history` (B, L), to history[b, positions[b]] (skipped when the
-// position is >= L); `u_out` (B,) fp32 receives the u that was used.
+// position is >= L); `u_out` (B,) fp32 receives the u that was used.  With rows_per_seq = R > 1 row r
+// is token r % R of sequence r / R: positions is (B / R,) and the counter
+// (positions[r / R] + position_offset + r % R, r / R, 0, 0).
 Tensor sample_tokens(const Tensor& logits, const Tensor& params, const c10::optional<Tensor>& u,
                      const c10::optional<Tensor>& seed, const c10::optional<Tensor>& positions,
-                     c10::optional<Tensor> out, c10::optional<Tensor> history, c10::optional<Tensor> u_out) {
+                     c10::optional<Tensor> out, c10::optional<Tensor> history, c10::optional<Tensor> u_out,
+                     int64_t rows_per_seq, int64_t position_offset) {
   check_bf16(logits, "logits");
   TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.size(1) >= 1, "sample_tokens: logits must be (B, V)");
   const int64_t B = logits.size(0), V = logits.size(1);
   TORCH_CHECK(V < (1LL << 31) && B < (1LL << 31), "sample_tokens: logits too large");
+  const int64_t R = rows_per_seq;
+  TORCH_CHECK(R >= 1 && B % R == 0, "sample_tokens: rows_per_seq must be >= 1 and divide the ", B, " rows, got ", R);
+  TORCH_CHECK(position_offset > -(1LL << 31) && position_offset < (1LL << 31), "sample_tokens: position_offset");
+  TORCH_CHECK(R == 1 || !given(history), "sample_tokens: history is not taken with rows_per_seq > 1");
   TORCH_CHECK(logits.stride(1) == 1, "sample_tokens: logits need unit stride on the vocabulary (inner stride)");
   const auto dev = logits.device();
   auto check_vec = [&](const Tensor& t, at::ScalarType ty, int64_t n, const char* name) {
@@ -1309,7 +1352,7 @@ Tensor sample_tokens(const Tensor& logits, const Tensor& params, const c10::opti
     p.seed = (const long*)seed->data_ptr<int64_t>();
   }
   if (given(positions)) {
-    check_vec(*positions, at::kInt, B, "positions");
+    check_vec(*positions, at::kInt, B / R, "positions");
     p.positions = positions->data_ptr<int>();
   }
   c10::hip::HIPGuardMasqueradingAsCUDA g(dev);
@@ -1341,8 +1384,61 @@ Tensor sample_tokens(const Tensor& logits, const Tensor& params, const c10::opti
   p.logits_rs = logits.stride(0);
   p.out_s = y.stride(0);
   p.B = (int)B; p.V = (int)V;
+  p.R = (int)R; p.pos_off = (int)position_offset;
   check_launch(orion_sample_tokens(p, cur_stream()), "sample_tokens");
   return y;
+}
+
+// ------------------------------------------------------------------ speculative decoding (csrc/spec_decode.hip)
+void check_spec_mat(const Tensor& t, int64_t B, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kLong && t.dim() == 2 && t.size(0) == B && t.size(1) >= 1 &&
+                  t.size(1) < (1LL << 31) && t.stride(1) == 1,
+              name, " must be an int64 (B, n) GPU tensor with unit inner stride");
+}
+
+void check_spec_vec(const Tensor& t, int64_t B, const Tensor& like, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device() && t.scalar_type() == at::kInt && t.dim() == 1 &&
+                  t.size(0) == B && t.is_contiguous(),
+              name, " must be a contiguous int32 (B,) tensor on the same device");
+}
+
+// out (B, k + 1): history[b, cur[b]], then k drafts continuing the latest earlier occurrence of the
+// row's last `ngram` tokens (columns [0, cur[b]] of history (B, L) are known).
+void spec_draft(const Tensor& history, const Tensor& cur, Tensor out, int64_t ngram) {
+  const int64_t B = history.dim() == 2 ? history.size(0) : 0;
+  TORCH_CHECK(B >= 1 && B < 65536, "spec_draft: history must be (B, L)");
+  check_spec_mat(history, B, "spec_draft: history");
+  check_spec_mat(out, B, "spec_draft: out");
+  check_spec_vec(cur, B, history, "spec_draft: cur");
+  TORCH_CHECK(out.device() == history.device(), "spec_draft: device mismatch");
+  TORCH_CHECK(ngram >= 1 && ngram < (1LL << 31), "spec_draft: ngram must be >= 1");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(history.device());
+  check_launch(orion_spec_draft((const long*)history.data_ptr<int64_t>(), history.stride(0), cur.data_ptr<int>(),
+                                (long*)out.data_ptr<int64_t>(), out.stride(0), (int)B, (int)history.size(1),
+                                (int)out.size(1), (int)ngram, cur_stream()),
+               "spec_draft");
+}
+
+// tokens / target (B, k + 1); start, lens, stop (B,) int32; history (B, L): the accept rule of a verify step.
+void spec_accept(const Tensor& tokens, const Tensor& target, const Tensor& start, Tensor lens, const Tensor& stop,
+                 Tensor history) {
+  const int64_t B = tokens.dim() == 2 ? tokens.size(0) : 0;
+  TORCH_CHECK(B >= 1, "spec_accept: tokens must be (B, k + 1)");
+  check_spec_mat(tokens, B, "spec_accept: tokens");
+  check_spec_mat(target, B, "spec_accept: target");
+  check_spec_mat(history, B, "spec_accept: history");
+  TORCH_CHECK(target.size(1) == tokens.size(1), "spec_accept: tokens and target must share a shape");
+  check_spec_vec(start, B, tokens, "spec_accept: start");
+  check_spec_vec(lens, B, tokens, "spec_accept: lens");
+  check_spec_vec(stop, B, tokens, "spec_accept: stop");
+  TORCH_CHECK(target.device() == tokens.device() && history.device() == tokens.device(), "spec_accept: device mismatch");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(tokens.device());
+  check_launch(orion_spec_accept((const long*)tokens.data_ptr<int64_t>(), tokens.stride(0),
+                                 (const long*)target.data_ptr<int64_t>(), target.stride(0), start.data_ptr<int>(),
+                                 lens.data_ptr<int>(), stop.data_ptr<int>(), (long*)history.data_ptr<int64_t>(),
+                                 history.stride(0), (int)B, (int)tokens.size(1) - 1, (int)history.size(1),
+                                 cur_stream()),
+               "spec_accept");
 }
 
 }  // namespace
@@ -1387,12 +1483,15 @@ TORCH_LIBRARY(orion_amd, m) {
   m.def("attn_fwd(Tensor q, Tensor k, Tensor v, bool causal, float scale) -> (Tensor, Tensor)");
   m.def("attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, bool causal, float scale, Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, int flags=0, Tensor(d!)? bias_grad=None, Tensor? rope_cos=None, Tensor? rope_sin=None, int rope_pos0=0) -> ()");
   m.def("attn_decode(Tensor q, Tensor k_cache, Tensor v_cache, Tensor kv_lens, float scale, int splits=0) -> Tensor");
+  m.def("attn_decode_multi(Tensor q, Tensor k_cache, Tensor v_cache, Tensor kv_lens, float scale, int splits=0) -> Tensor");
   m.def("kv_append(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor kv_lens, Tensor? q=None, Tensor? cos=None, Tensor? sin=None) -> Tensor");
   m.def("attn_decode_fp8(Tensor q, Tensor k_cache, Tensor v_cache, Tensor k_scale, Tensor v_scale, Tensor kv_lens, float scale, int splits=0) -> Tensor");
   m.def("kv_append_fp8(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor(c!) k_scale, Tensor(d!) v_scale, Tensor kv_lens, Tensor? q=None, Tensor? cos=None, Tensor? sin=None) -> Tensor");
   m.def("linear_decode(Tensor x, Tensor w, Tensor? bias, int norm, Tensor? norm_w, Tensor? norm_b, float eps, int act, Tensor? residual, Tensor(a!)? out=None) -> Tensor");
   m.def("linear_decode_fp8(Tensor x, Tensor wq, Tensor w_scale, Tensor? bias, int norm, Tensor? norm_w, Tensor? norm_b, float eps, int act, Tensor? residual, Tensor(a!)? out=None) -> Tensor");
-  m.def("sample_tokens(Tensor logits, Tensor params, Tensor? u, Tensor? seed, Tensor? positions, Tensor(a!)? out=None, Tensor(b!)? history=None, Tensor(c!)? u_out=None) -> Tensor");
+  m.def("sample_tokens(Tensor logits, Tensor params, Tensor? u, Tensor? seed, Tensor? positions, Tensor(a!)? out=None, Tensor(b!)? history=None, Tensor(c!)? u_out=None, int rows_per_seq=1, int position_offset=0) -> Tensor");
+  m.def("spec_draft(Tensor history, Tensor cur, Tensor(a!) out, int ngram) -> ()");
+  m.def("spec_accept(Tensor tokens, Tensor target, Tensor start, Tensor(a!) lens, Tensor stop, Tensor(b!) history) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(orion_amd, CUDA, m) {
@@ -1437,4 +1536,7 @@ TORCH_LIBRARY_IMPL(orion_amd, CUDA, m) {
   m.impl("linear_decode", &linear_decode);
   m.impl("linear_decode_fp8", &linear_decode_fp8);
   m.impl("sample_tokens", &sample_tokens);
+  m.impl("attn_decode_multi", &attn_decode_multi);
+  m.impl("spec_draft", &spec_draft);
+  m.impl("spec_accept", &spec_accept);
 }

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "attn_decode_fp8_params.h"
+#include "attn_decode_multi_params.h"
 #include "attn_decode_params.h"
 #include "attn_plan.h"
 #include "linear_decode_fp8_params.h"
@@ -111,7 +112,8 @@ int orion_lmhead_bwd_prep(const void* X, long ldx, int Cdim, long N, const int64
                           const float* invz, const float* inv_n, const float* g, float* srow, void* Xs,
                           int transposed, hipStream_t st);
 
-// attn_decode.hip, attn_decode_fp8.hip, linear_decode.hip, linear_decode_fp8.hip, sample.hip: generation
+// attn_decode.hip, attn_decode_fp8.hip, attn_decode_multi.hip, linear_decode.hip, linear_decode_fp8.hip,
+// sample.hip, spec_decode.hip: generation
 // (negative: a field of p failed its check)
 int orion_attn_decode_split_plan(int tile, int B, int Hkv, int Tmax, int splits, int* chunk);  // key tiles of `tile`
 int orion_attn_decode_plan(int B, int Hkv, int Tmax, int D, int splits, int* chunk);
@@ -126,3 +128,11 @@ int orion_kv_append_fp8(const orion::AppendFp8Params& p, hipStream_t st);
 int orion_linear_decode(const orion::LinearDecodeParams& p, hipStream_t st);
 int orion_linear_decode_fp8(const orion::LinearDecodeFp8Params& p, hipStream_t st);  // -1 also K % 16
 int orion_sample_tokens(const orion::SampleParams& p, hipStream_t st);
+// Tq <= 16 queries per row with a causal tail; splits / chunk from orion_attn_decode_plan (-2 also: another tile)
+int orion_attn_decode_multi(const orion::DecodeMultiParams& p, int D, hipStream_t st);
+// spec_decode.hip: out (B, k1) = the current token and k1 - 1 n-gram drafts; the accept rule of a verify step
+int orion_spec_draft(const long* history, long hist_rs, const int* cur, long* out, long out_rs, int B, int L,
+                     int k1, int ngram, hipStream_t st);
+int orion_spec_accept(const long* tokens, long tok_rs, const long* target, long tgt_rs, const int* start,
+                      int* lens, const int* stop, long* history, long hist_rs, int B, int k, int L,
+                      hipStream_t st);

@@ -28,7 +28,10 @@
 //     stored (the last kept index when there is none: NaN or -inf rows).  No float atomics: two launches on
 //     the same inputs store the same tokens.
 //   * u is given, or Philox4x32-10 with the 64-bit seed as key and (positions[b], b, 0, 0) as
-//     counter: no state is advanced, so workgroups do not race.
+//     counter: no state is advanced, so workgroups do not race.  With R > 1 rows per sequence (a
+//     verify step of speculative decoding) row r is token r % R of sequence s = r / R and draws
+//     from (positions[s] + pos_off + r % R, s, 0, 0): the counter a one-row step at that position
+//     would use.
 //   * A row of NaN or of -inf only makes every comparison false and takes the last-kept exit, so
 //     the token stays in [0, V).
 #include <limits.h>
@@ -155,8 +158,10 @@ __global__ __launch_bounds__(SP_NT) void sample_kernel(const SampleParams p) {
       u = p.u[b];
     } else {
       const unsigned long long seed = (unsigned long long)p.seed[0];
-      const unsigned x0 = sp_philox_x0((unsigned)p.positions[b], (unsigned)b, 0u, 0u, (unsigned)seed,
-                                       (unsigned)(seed >> 32));
+      const int R = p.R > 1 ? p.R : 1, sq = b / R;
+      ORION_DASSERT(sq * R < p.B);
+      const unsigned x0 = sp_philox_x0((unsigned)(p.positions[sq] + p.pos_off + (b - sq * R)), (unsigned)sq, 0u, 0u,
+                                       (unsigned)seed, (unsigned)(seed >> 32));
       // rounded to fp32; the largest word's sum is a tie that rounds to 1.0, hence the cap
       u = fminf((float)(x0 >> 8) * 0x1p-24f + 0x1p-25f, 0x1.fffffep-1f);
     }
@@ -332,7 +337,8 @@ int orion_sample_tokens(const SampleParams& p, hipStream_t st) {
   if (p.B < 1 || p.V < 1) return -1;
   if (!p.logits || !p.params || !p.out_tokens) return -2;
   if (!p.u && (!p.seed || !p.positions)) return -3;
-  if (p.history && (!p.positions || p.L < 1)) return -4;
+  if (p.history && (!p.positions || p.L < 1 || p.R > 1)) return -4;
+  if (p.R < 0 || (p.R > 1 && p.B % p.R)) return -1;
   const long nslots = ((long)p.V + 7 + 7) / 8;  // the most slots a row of V can take (a <= 7)
   if (nslots <= SP_STAGE_SLOTS) {
     constexpr int lds = SP_STAGE_SLOTS * 16;

@@ -10,12 +10,15 @@ struct SampleParams {
   const int* params;             // [0] fp32 bits of the temperature, [1] top_k (<= 0 or >= V: all)
   const float* u;                // (B,) uniforms in (0, 1), or null: Philox from seed / positions
   const long* seed;              // one 64-bit Philox key (with u == null)
-  const int* positions;          // (B,): Philox counter word 0 and the history column, or null
+  const int* positions;          // (B / R,): Philox counter word 0 and the history column, or null
   long* out_tokens;              // (B,) with stride out_s
   long* history;                 // (B, L) with row stride history_rs, or null (needs positions)
   float* u_out;                  // (B,) the u that was used, or null
   long logits_rs, out_s, history_rs;
   int B, V, L;
+  // Rows per sequence (>= 1; 0 reads as 1): row r is token t = r % R of sequence r / R, and its
+  // counter is (positions[r / R] + pos_off + t, r / R, 0, 0).  history needs R == 1.
+  int R, pos_off;
 };
 
 }  // namespace orion

@@ -19,6 +19,31 @@ from ..ops.decode import MAX_ROWS as MAX_GRAPH_BATCH  # rows of ops.linear_decod
 from . import generation
 
 
+def check_speculative(speculative, ngram, draft, batch, sampler, kv):
+    """Raise ``ValueError`` unless ``speculative`` is None or a speculative session of ``batch`` rows
+    can be built with these settings."""
+    if speculative is None:
+        return
+    k = int(speculative)
+    if sampler != "device":
+        raise ValueError(f"speculative decoding verifies the device sampler's draws: sampler must be 'device', "
+                         f"got {sampler!r}")
+    if kv != "bf16":
+        raise ValueError(f"speculative decoding needs a bf16 key/value cache (the multi-query attention kernel "
+                         f"has no FP8 variant), got kv={kv!r}")
+    if k < 1 or int(batch) * (k + 1) > MAX_GRAPH_BATCH:
+        raise ValueError(f"speculative must be >= 1 with batch * (speculative + 1) <= {MAX_GRAPH_BATCH} (the rows "
+                         f"of the skinny linear kernel), got speculative={speculative} at batch {batch}")
+    if isinstance(draft, torch.Tensor):
+        if draft.dim() != 2 or draft.shape[0] != int(batch) or draft.dtype != torch.int64 or draft.shape[1] < 1:
+            raise ValueError(f"draft must be 'ngram' or an int64 (batch, L) tensor, got {tuple(draft.shape)} "
+                             f"{draft.dtype}")
+    elif draft != "ngram":
+        raise ValueError(f"draft must be 'ngram' or an int64 (batch, L) tensor, got {draft!r}")
+    elif int(ngram) < 1:
+        raise ValueError(f"ngram must be >= 1, got {ngram}")
+
+
 class DecodeSession:
     """One key/value cache, a static (B, 1) token buffer and a static (B, vocab) logits buffer for
     a model that has ``new_cache``, ``forward_cached``, ``decode_step`` and ``decode_projections``
@@ -56,15 +81,34 @@ class DecodeSession:
     each layer dequantised to a transient (``KVCache.dense_layer``), so a chunked prompt and the
     decode steps see the same keys and values; the transient is one layer's k and v in the
     activation dtype at a time.  With the default ``"bf16"`` the cache is built as without the
-    keyword."""
+    keyword.
 
-    def __init__(self, model, batch, max_len=None, graph=False, sampler="torch", weights="bf16", kv="bf16"):
+    ``speculative=k`` (with ``sampler="device"``, a bf16 cache and batch (k + 1) <= 16) makes
+    :meth:`generate` emit up to k + 1 tokens per step: k guesses are verified by one
+    ``decode_step`` over the current token and the guesses, the target token of every one of the
+    k + 1 positions is drawn with the Philox counter the plain loop uses at that position, and the
+    longest prefix of guesses that equal those draws is kept (``ops.spec_accept``).  The tokens are
+    therefore those of the plain ``sampler="device"`` loop under the same seed, token for token.
+    The guesses come from ``ops.spec_draft`` on ``history`` (``draft="ngram"``: the continuation
+    of the latest earlier occurrence of the last ``ngram`` tokens) or from ``draft`` (B, L) int64,
+    guesses indexed by sequence position (read at clamped columns).  The session then also owns
+    ``spec_tokens`` / ``spec_target`` (B, k + 1) int64, ``spec_logits`` (B (k + 1), vocab) and
+    ``stop`` (B,) int32, ``history`` also receives the prompt at :meth:`prefill`, and the step
+    (draft, forward, draws, accept) is one captured linear chain with ``graph=True``.  The rows'
+    lengths differ between steps: the host reads ``cache.lens`` back once per step (the step's one
+    synchronisation) and keeps ``cache.pos`` at their maximum.  ``spec_steps`` counts the verify
+    steps and ``spec_emitted`` the tokens they produced.  With the default ``None`` nothing
+    changes."""
+
+    def __init__(self, model, batch, max_len=None, graph=False, sampler="torch", weights="bf16", kv="bf16",
+                 speculative=None, ngram=3, draft="ngram"):
         if sampler not in ("torch", "device"):
             raise ValueError(f"sampler must be 'torch' or 'device', got {sampler!r}")
         if weights not in ("bf16", "fp8"):
             raise ValueError(f"weights must be 'bf16' or 'fp8', got {weights!r}")
         if kv not in ("bf16", "fp8"):
             raise ValueError(f"kv must be 'bf16' or 'fp8', got {kv!r}")
+        check_speculative(speculative, ngram, draft, batch, sampler, kv)
         cfg = model.config
         self.model = model
         self.batch = int(batch)
@@ -80,6 +124,8 @@ class DecodeSession:
         self.weight_bytes = sum(pw.nbytes for _, pw in projections)
         # what the model's calls get beyond their usual arguments: nothing for a bf16 session
         self._model_kw = {} if self.qweights is None else {"weights": self.qweights}
+        self.speculative = None if speculative is None else int(speculative)
+        rows = self.batch * (1 + (self.speculative or 0))  # of a step's linear layers
         if self.graph and self.on_gpu:
             if self.batch > MAX_GRAPH_BATCH:
                 raise ValueError(f"DecodeSession(graph=True): batch {self.batch} > {MAX_GRAPH_BATCH}, the most "
@@ -88,7 +134,7 @@ class DecodeSession:
             for name, pw in projections:
                 K = pw.shape[1]
                 if K not in probes:
-                    probes[K] = torch.empty(self.batch, K, device=w.device, dtype=w.dtype)
+                    probes[K] = torch.empty(rows, K, device=w.device, dtype=w.dtype)
                 if not ops.linear_decode_eligible(probes[K], pw):
                     kind = (f"{pw.dtype}", "K % 8 == 0") if self.qweights is None else \
                         ("fp8 (e4m3, bf16 activations)", "K % 16 == 0")
@@ -112,12 +158,29 @@ class DecodeSession:
             self.rng_seed = torch.zeros(1, dtype=torch.int64, device=w.device)
             self.sample_params = sample_params(1.0, None, w.device)
             self.history = torch.zeros(self.batch, self.max_len + 1, dtype=torch.long, device=w.device)
+        self.ngram = int(ngram)
+        self.draft = None
+        self.spec_steps = self.spec_emitted = 0
+        self._spec_graph = None
+        if self.speculative is not None:
+            k1 = self.speculative + 1
+            if isinstance(draft, torch.Tensor):
+                self.draft = draft.to(w.device)
+                self._draft_cols = torch.arange(k1, device=w.device).view(1, k1)
+            self.spec_tokens = torch.zeros(self.batch, k1, dtype=torch.long, device=w.device)
+            self.spec_target = torch.zeros(self.batch, k1, dtype=torch.long, device=w.device)
+            self.spec_logits = torch.zeros(self.batch * k1, cfg.vocab_size, dtype=w.dtype, device=w.device)
+            self.stop = torch.zeros(self.batch, dtype=torch.int32, device=w.device)
 
     # ------------------------------------------------------------------ prompt
     @torch.no_grad()
     def prefill(self, idx):
         """The model's ``forward_cached`` on this session's cache: logits (B, vocab) of the last
-        position of ``idx`` (B, T); call it again for a chunked prompt."""
+        position of ``idx`` (B, T); call it again for a chunked prompt.  A speculative session
+        also keeps the prompt in ``history``, for the n-gram draft to search."""
+        if self.speculative is not None:
+            pos = self.cache.pos
+            self.history[:, pos:pos + idx.shape[1]] = idx[:, :max(0, self.history.shape[1] - pos)]
         return self.model.forward_cached(idx, self.cache, **self._model_kw)
 
     def reset(self):
@@ -179,6 +242,8 @@ class DecodeSession:
         With the default sampler, sampling stays outside the captured step, on the static logits,
         and the new tokens go into a preallocated output; ``sampler="device"`` is
         :meth:`_generate_device`."""
+        if self.speculative is not None:
+            return self._generate_speculative(idx, n, temperature, top_k)
         if self.sampler == "device":
             return self._generate_device(idx, n, temperature, top_k)
         B, T = idx.shape
@@ -240,4 +305,71 @@ class DecodeSession:
         self._sample(logits)
         for _ in range(n - 1):
             self._step_sample()
+        return torch.cat((idx, self.history[:, p0:p0 + n].to(idx.dtype)), dim=1)
+
+    # ------------------------------------------------------------------ speculative decoding
+    def _spec_body(self):
+        """One verify step on device state only: start <- lens, lens += k + 1, the current token
+        and the k guesses into ``spec_tokens``, the forward over them, the draw of the target token
+        at every position (the counter of position start + 1 + t), and the accept rule, which
+        writes the emitted tokens into ``history`` and the rows' new lengths into ``cache.lens``."""
+        cache, k1 = self.cache, self.speculative + 1
+        cache.start.copy_(cache.lens)
+        cache.lens.add_(k1)
+        if self.draft is None:
+            ops.spec_draft(self.history, cache.start, self.spec_tokens, self.ngram)
+        else:
+            cols = cache.start.view(-1, 1).long() + self._draft_cols
+            self.spec_tokens.copy_(self.draft.gather(1, cols.clamp(0, self.draft.shape[1] - 1)))
+            self.spec_tokens[:, :1] = self.history.gather(1, cols[:, :1].clamp(0, self.history.shape[1] - 1))
+        self.model.decode_step(self.spec_tokens, cache, self.spec_logits, **self._model_kw)
+        ops.sample_tokens(self.spec_logits, params=self.sample_params, seed=self.rng_seed, positions=cache.start,
+                          out=self.spec_target.view(-1), rows_per_seq=k1, position_offset=1)
+        ops.spec_accept(self.spec_tokens, self.spec_target, cache.start, cache.lens, self.stop, self.history)
+
+    def _step_speculative(self):
+        """One verify step (a replay of its one graph with ``graph=True``; every replay counts in
+        ``replays``), then the step's one synchronisation: the rows' lengths come back to the host.
+        Returns them."""
+        cache = self.cache
+        if not (self.graph and self.on_gpu):
+            self._spec_body()
+        else:
+            if self._spec_graph is None:
+                # the warm-up's appends land where the first replay's land; the rest is put back
+                self._spec_graph = self._capture(self._spec_body, (cache.lens, cache.start, self.spec_tokens,
+                                                                   self.spec_target, self.history))
+            self._spec_graph.replay()
+            self.replays += 1
+        lens = cache.lens.tolist()
+        self.spec_steps += 1
+        return lens
+
+    def _generate_speculative(self, idx, n, temperature, top_k):
+        """:meth:`_generate_device` with up to k + 1 tokens per step.  The seed, the sampling
+        parameters, the prefill and the first token are that method's; every later token comes
+        from verify steps until each row has reached ``stop[b]`` = the column of its n-th token
+        (a row that is done emits nothing more).  The tokens are those of the plain loop."""
+        from ..ops.decode import sample_params
+        B, T = idx.shape
+        p0 = self.cache.pos + T
+        if n < 1:
+            return idx.clone()
+        self.cache.check_room(T + n - 1)
+        seed = torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64)
+        self.rng_seed.copy_(seed)
+        sample_params(temperature, top_k, out=self.sample_params)
+        logits = self.prefill(idx)
+        self._sample(logits)
+        last = p0 + n - 1
+        self.stop.fill_(last)
+        lens = [p0] * B
+        while min(lens) < last:
+            new = self._step_speculative()
+            emitted = sum(new) - sum(lens)
+            if emitted <= 0:
+                raise RuntimeError(f"speculative step emitted no token (lengths {lens} -> {new})")
+            self.spec_emitted += emitted
+            lens = new
+            self.cache.pos = max(lens)
         return torch.cat((idx, self.history[:, p0:p0 + n].to(idx.dtype)), dim=1)

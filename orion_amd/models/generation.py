@@ -39,17 +39,23 @@ def sample_logits(logits, temperature=1.0, top_k=None):
 class Generation:
     """``generate`` and ``decode_session`` of a model with a :class:`KVCache`."""
 
-    def decode_session(self, batch, max_len=None, graph=False, sampler="torch", weights="bf16", kv="bf16"):
+    def decode_session(self, batch, max_len=None, graph=False, sampler="torch", weights="bf16", kv="bf16",
+                       speculative=None, ngram=3, draft="ngram"):
         """A :class:`DecodeSession` for this model: the fused decode step, captured when ``graph``;
         ``sampler="device"`` draws the tokens with ``ops.sample_tokens`` inside that step,
         ``weights="fp8"`` decodes from per-row e4m3 copies of the projection weights and
-        ``kv="fp8"`` keeps the key/value cache as e4m3 bytes with one scale per (token, KV head)."""
+        ``kv="fp8"`` keeps the key/value cache as e4m3 bytes with one scale per (token, KV head).
+        ``speculative=k`` verifies k guessed tokens per step (``draft="ngram"`` with ``ngram``, or a
+        (batch, L) tensor of guesses by position) and emits the plain loop's tokens."""
         from .decode_session import DecodeSession
-        return DecodeSession(self, batch, max_len, graph=graph, sampler=sampler, weights=weights, kv=kv)
+        if speculative is None:
+            return DecodeSession(self, batch, max_len, graph=graph, sampler=sampler, weights=weights, kv=kv)
+        return DecodeSession(self, batch, max_len, graph=graph, sampler=sampler, weights=weights, kv=kv,
+                             speculative=speculative, ngram=ngram, draft=draft)
 
     @torch.no_grad()
     def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, use_cache=False, sampler="torch",
-                 weights="bf16", kv="bf16"):
+                 weights="bf16", kv="bf16", speculative=None, ngram=3, draft="ngram"):
         """nanoGPT's sampling loop.  ``use_cache=True`` keeps every layer's keys / values
         (:class:`KVCache`): the prompt is prefilled once and each new token costs one single-token
         forward.  Tokens beyond the context limit (``block_size`` / ``max_seq_len``) take the
@@ -64,7 +70,14 @@ class Generation:
         keeps using the model's own (unquantised) weights, as it keeps clear of the session.
         ``kv="fp8"`` (with ``use_cache`` True, ``"fused"`` or ``"graph"``) keeps the cache as e4m3
         bytes with one fp32 scale per (token, KV head): about half the cache's memory and bytes per
-        step; the sliding-window loop has no cache and does not change."""
+        step; the sliding-window loop has no cache and does not change.
+        ``speculative=k`` (``use_cache`` ``"fused"`` or ``"graph"``, ``sampler="device"``, a bf16
+        cache, B (k + 1) <= 16) makes the session verify k guessed tokens per step and keep those
+        that equal its own draws (:class:`DecodeSession`): the same tokens as without it under the
+        same ``torch.manual_seed``, in fewer steps when the guesses are good.  ``draft="ngram"``
+        guesses the continuation of the latest earlier occurrence of the last ``ngram`` tokens;
+        a (B, L) int64 tensor gives the guesses by sequence position.  The sliding-window loop
+        does not change."""
         fused = isinstance(use_cache, str)
         if fused and use_cache not in ("fused", "graph"):
             raise ValueError(f"use_cache must be False, True, 'fused' or 'graph', got {use_cache!r}")
@@ -83,13 +96,19 @@ class Generation:
         if kv == "fp8" and not use_cache:
             raise ValueError("kv='fp8' is the key/value cache's format: use_cache must be True, 'fused' or "
                              f"'graph', got {use_cache!r}")
-        limit = self.context_len
         B, T = idx.shape
+        if speculative is not None:
+            from .decode_session import check_speculative
+            if not fused:
+                raise ValueError("speculative decoding runs through the fused decode step: use_cache must be "
+                                 f"'fused' or 'graph', got {use_cache!r}")
+            check_speculative(speculative, ngram, draft, B, sampler, kv)
+        limit = self.context_len
         if use_cache and max_new_tokens > 0 and T < limit:
             n = min(max_new_tokens, limit - T + 1)  # the n-th token is drawn from position limit - 1's logits
             if fused:
                 sess = self.decode_session(B, T + n - 1, graph=use_cache == "graph", sampler=sampler,
-                                           weights=weights, kv=kv)
+                                           weights=weights, kv=kv, speculative=speculative, ngram=ngram, draft=draft)
                 idx = sess.generate(idx, n, temperature, top_k)
             else:
                 cache = self.new_cache(B, T + n - 1, kv_dtype=kv)

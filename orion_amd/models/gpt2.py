@@ -272,23 +272,38 @@ class GPT(nn.Module, Generation):
         the logits of ``tokens`` (B, 1) at position ``cache.start`` go into ``logits_out``.  Every
         projection is one ``ops.linear_decode`` with the norm in its prologue and the bias /
         GELU / residual in its epilogue; the session has advanced ``cache.start`` / ``cache.lens``.
-        A projection named in ``weights`` (name -> ``ops.Fp8Weight``) streams that weight."""
+        A projection named in ``weights`` (name -> ``ops.Fp8Weight``) streams that weight.
+
+        ``tokens`` (B, Tq) with B Tq <= 16 is a speculative verify step: token t of row b sits at
+        position ``cache.start[b] + t``, every projection runs on the B Tq rows, the Tq keys /
+        values are appended by one ``ops.kv_append`` and attended by one
+        ``ops.attention_decode_multi``, and ``logits_out`` is (B Tq, vocab).  A position past the
+        end of the cache (near the context limit) takes the last position's embedding and is
+        skipped by the append: its logits are finite and never used."""
         cfg, tr = self.config, self.transformer
-        B, H, D = tokens.shape[0], cfg.n_head, cfg.head_dim
-        x = F.embedding(tokens[:, 0], tr.wte.weight) + F.embedding(cache.start, tr.wpe.weight)
+        (B, Tq), H, D = tokens.shape, cfg.n_head, cfg.head_dim
+        if Tq == 1:
+            x = F.embedding(tokens[:, 0], tr.wte.weight) + F.embedding(cache.start, tr.wpe.weight)
+        else:
+            pos = cache.start.view(B, 1) + torch.arange(Tq, device=tokens.device, dtype=cache.start.dtype)
+            x = F.embedding(tokens, tr.wte.weight) + F.embedding(pos.clamp_(max=cfg.block_size - 1), tr.wpe.weight)
+            x = x.view(B * Tq, -1)
         ws = session_weights(self, weights)
         for i, blk in enumerate(tr.h):
             at, ml = blk.attn, blk.mlp
             w_qkv, w_o, w_fc, w_pr = (at.c_attn.weight, at.c_proj.weight, ml.c_fc.weight, ml.c_proj.weight) \
                 if ws is None else ws[4 * i:4 * i + 4]
             qkv = ops.linear_decode(x, w_qkv, at.c_attn.bias, norm="layer", norm_weight=blk.ln_1.weight,
-                                    norm_bias=blk.ln_1.bias).view(B, 1, 3, H, D)
+                                    norm_bias=blk.ln_1.bias).view(B, Tq, 3, H, D)
             kc, vc = cache.layer(i)
             ks, vs = cache.layer_scales(i)
             ops.kv_append(qkv[:, :, 1], qkv[:, :, 2], kc, vc, cache.start, k_scale=ks, v_scale=vs)
             # the whole cache view: the key split is planned from max_len once and never changes
-            y = ops.attention_decode(qkv[:, 0, 0], kc, vc, cache.lens, k_scale=ks, v_scale=vs)
-            x = ops.linear_decode(y.view(B, H * D), w_o, at.c_proj.bias, residual=x)
+            if Tq == 1:
+                y = ops.attention_decode(qkv[:, 0, 0], kc, vc, cache.lens, k_scale=ks, v_scale=vs)
+            else:
+                y = ops.attention_decode_multi(qkv[:, :, 0], kc, vc, cache.lens)
+            x = ops.linear_decode(y.view(B * Tq, H * D), w_o, at.c_proj.bias, residual=x)
             h = ops.linear_decode(x, w_fc, ml.c_fc.bias, norm="layer", norm_weight=blk.ln_2.weight,
                                   norm_bias=blk.ln_2.bias, act="gelu")
             x = ops.linear_decode(h, w_pr, ml.c_proj.bias, residual=x)

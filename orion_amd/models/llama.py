@@ -241,11 +241,17 @@ class Llama(nn.Module, Generation):
         the logits of ``tokens`` (B, 1) at position ``cache.start`` go into ``logits_out``.  Every
         projection is one ``ops.linear_decode`` with the norm in its prologue and the SwiGLU /
         residual in its epilogue; the session has advanced ``cache.start`` / ``cache.lens``.
-        A projection named in ``weights`` (name -> ``ops.Fp8Weight``) streams that weight."""
+        A projection named in ``weights`` (name -> ``ops.Fp8Weight``) streams that weight.
+
+        ``tokens`` (B, Tq) with B Tq <= 16 is a speculative verify step: token t of row b sits at
+        position ``cache.start[b] + t``, every projection runs on the B Tq rows, the Tq keys /
+        values are appended (and rotated) by one ``ops.kv_append`` and attended by one
+        ``ops.attention_decode_multi``, and ``logits_out`` is (B Tq, vocab).  A position past the
+        end of the cache is skipped by the append (its q is zero): its logits are never used."""
         cfg = self.config
-        B, Hq, Hkv, D = tokens.shape[0], cfg.n_heads, cfg.n_kv_heads, cfg.head_dim
+        (B, Tq), Hq, Hkv, D = tokens.shape, cfg.n_heads, cfg.n_kv_heads, cfg.head_dim
         cos, sin = self.rope_cos, self.rope_sin
-        x = F.embedding(tokens[:, 0], self.embed_tokens.weight)
+        x = F.embedding(tokens[:, 0] if Tq == 1 else tokens.reshape(B * Tq), self.embed_tokens.weight)
         ws = session_weights(self, weights)
         for i, layer in enumerate(self.layers):
             at, ff = layer.self_attn, layer.mlp
@@ -253,13 +259,16 @@ class Llama(nn.Module, Generation):
             w_qkv, w_o, w_gu, w_dn = (at.qkv_proj.weight, at.o_proj.weight, ff.gate_up_proj.weight,
                                       ff.down_proj.weight) if ws is None else ws[4 * i:4 * i + 4]
             qkv = ops.linear_decode(x, w_qkv, norm="rms", norm_weight=ln1.weight,
-                                    eps=ln1.eps).view(B, 1, Hq + 2 * Hkv, D)
+                                    eps=ln1.eps).view(B, Tq, Hq + 2 * Hkv, D)
             kc, vc = cache.layer(i)
             ks, vs = cache.layer_scales(i)
             q = ops.kv_append(qkv[:, :, Hq:Hq + Hkv], qkv[:, :, Hq + Hkv:], kc, vc, cache.start,
                               q=qkv[:, :, :Hq], cos=cos, sin=sin, k_scale=ks, v_scale=vs)
-            y = ops.attention_decode(q[:, 0], kc, vc, cache.lens, k_scale=ks, v_scale=vs)
-            x = ops.linear_decode(y.view(B, Hq * D), w_o, residual=x)
+            if Tq == 1:
+                y = ops.attention_decode(q[:, 0], kc, vc, cache.lens, k_scale=ks, v_scale=vs)
+            else:
+                y = ops.attention_decode_multi(q, kc, vc, cache.lens)
+            x = ops.linear_decode(y.view(B * Tq, Hq * D), w_o, residual=x)
             h = ops.linear_decode(x, w_gu, norm="rms", norm_weight=ln2.weight, eps=ln2.eps,
                                   act="swiglu")
             x = ops.linear_decode(h, w_dn, residual=x)

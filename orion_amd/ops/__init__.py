@@ -347,6 +347,70 @@ def attention_decode(q, k_cache, v_cache, kv_lens, scale=None, splits=0, k_scale
     return ref.attention_decode(q, k_cache, v_cache, kv_lens, scale, k_scale, v_scale)
 
 
+def attention_decode_multi(q, k_cache, v_cache, kv_lens, scale=None, splits=0):
+    """A few queries per row against a key/value cache with a causal tail, the attention of a
+    speculative verify step: q (B, Tq, Hq, D) with 1 <= Tq <= 16, bf16 caches (B, Tmax, Hkv, D),
+    kv_lens (B,) int32 including the Tq tokens of the forward in progress -> (B, Tq, Hq, D).
+    Query t of row b attends keys [0, lim), lim = clamp(kv_lens[b] - Tq + 1 + t, 0,
+    min(kv_lens[b], Tmax)); a query with lim = 0 yields zeros and keys at or beyond
+    min(kv_lens[b], Tmax) are never loaded.  On the GPU one launch of csrc/attn_decode_multi.hip
+    (plus the combine of the key splits), whose output [:, t] equals bit for bit
+    ``attention_decode(q[:, t], ..., kv_lens - (Tq - 1 - t), splits=splits)``: ``splits`` means
+    what it means there (0: planned from Tmax).  An FP8 cache raises ``ValueError``.  Inference
+    only."""
+    if k_cache.dtype == torch.float8_e4m3fn or v_cache.dtype == torch.float8_e4m3fn:
+        raise ValueError("attention_decode_multi takes bf16 caches only: an FP8 cache has no multi-query kernel")
+    if q.dim() != 4 or not 1 <= q.shape[1] <= 16:
+        raise ValueError(f"attention_decode_multi: q must be (B, Tq, Hq, D) with 1 <= Tq <= 16, got {tuple(q.shape)}")
+    b = _gpu(q)
+    if b == "hip":
+        from .decode import attention_decode_multi_hip
+        return attention_decode_multi_hip(q, k_cache, v_cache, kv_lens, scale, splits)
+    if b == "torch":
+        from .decode import attention_decode_multi_torch
+        return attention_decode_multi_torch(q, k_cache, v_cache, kv_lens, scale)
+    return ref.attention_decode_multi(q, k_cache, v_cache, kv_lens, scale)
+
+
+def spec_draft(history, cur, out, ngram=3):
+    """The n-gram draft of a speculative step: history (B, L) int64 whose columns [0, cur[b]] are
+    known, cur (B,) int32, out (B, k + 1) int64, overwritten: out[b, 0] = history[b, cur[b]], and
+    the k drafts continue the latest earlier occurrence of the row's last ``ngram`` tokens
+    (periodically once the continuation runs into the present); without such an occurrence every
+    draft is the current token (``ref.spec_draft`` states the rule).  One launch on the GPU,
+    reading ``cur`` on the device; integer-exact."""
+    if int(ngram) < 1:
+        raise ValueError(f"spec_draft: ngram must be >= 1, got {ngram}")
+    if history.is_cuda and _BACKEND == "hip":
+        from .decode import spec_draft_hip
+        return spec_draft_hip(history, cur, out, ngram)
+    if history.is_cuda:
+        out.copy_(ref.spec_draft(history.cpu(), cur.cpu(), out.cpu(), ngram))
+        return out
+    return ref.spec_draft(history, cur, out, ngram)
+
+
+def spec_accept(tokens, target, start, lens, stop, history):
+    """The accept rule of a speculative step: tokens (B, k + 1) int64 (the current token, then the
+    drafts), target (B, k + 1) int64 (target[b, t] drawn from the logits of input t: the token at
+    column start[b] + 1 + t), start / lens / stop (B,) int32, history (B, L) int64.  With a the
+    number of leading drafts that equal the draw before them, e = clamp(min(a + 1, stop[b] -
+    start[b]), 0, k + 1) tokens are emitted: history[b, start[b] + 1 + i] = target[b, i] for
+    i < e (columns >= L skipped), lens[b] = start[b] + e, and nothing else is written.  One launch
+    on the GPU, on device state only."""
+    if tokens.is_cuda and _BACKEND == "hip":
+        from .decode import spec_accept_hip
+        return spec_accept_hip(tokens, target, start, lens, stop, history)
+    if tokens.is_cuda:
+        h, n = history.cpu(), lens.cpu()
+        ref.spec_accept(tokens.cpu(), target.cpu(), start.cpu(), n, stop.cpu(), h)
+        history.copy_(h)
+        lens.copy_(n)
+        return None
+    ref.spec_accept(tokens, target, start, lens, stop, history)
+    return None
+
+
 def kv_append(k_new, v_new, k_cache, v_cache, kv_lens, q=None, cos=None, sin=None, k_scale=None, v_scale=None):
     """Write k_new / v_new (B, T, Hkv, D) into the caches at positions kv_lens[b] + t (skipping
     positions >= Tmax; kv_lens itself is unchanged).  With fp32 tables (``ref.rope_tables``) k is
@@ -435,7 +499,7 @@ def sample_tokens_eligible(logits):
 
 
 def sample_tokens(logits, temperature=1.0, top_k=None, *, u=None, seed=None, positions=None, out=None,
-                  history=None, params=None, u_out=None):
+                  history=None, params=None, u_out=None, rows_per_seq=1, position_offset=0):
     """One token per row of logits (B, V) -> (B, 1) int64 by the models' sampling rule with an
     explicit uniform: z = logits / max(temperature, 1e-6); with ``top_k`` only the entries >= the
     k-th largest of the row are kept (ties at the threshold all stay; None, <= 0 or >= V keeps
@@ -445,7 +509,11 @@ def sample_tokens(logits, temperature=1.0, top_k=None, *, u=None, seed=None, pos
     keyed by the 64-bit ``seed`` (an int or a (1,) int64 tensor) at counter (positions[b], b, 0, 0),
     ``positions`` (B,) int32, so no generator state is advanced.  ``out`` (B,) or (B, 1) int64
     takes the token in place, ``history`` (B, L) int64 also gets it at column positions[b] (skipped
-    when that is >= L) and ``u_out`` (B,) fp32 the u that was used.
+    when that is >= L) and ``u_out`` (B,) fp32 the u that was used.  With ``rows_per_seq`` = R
+    row r of the (B R, V) logits belongs to sequence b = r // R at t = r % R and its counter is
+    (positions[b] + position_offset + t, b, 0, 0): the draws of R consecutive positions of every
+    sequence in one launch (a speculative verify step); ``positions`` stays (B,) and ``history``
+    is refused.
 
     On the GPU one launch when :func:`sample_tokens_eligible` (bf16 on the HIP backend), reading
     the temperature and top_k from ``params`` (``ops.decode.sample_params``; built from the two
@@ -455,6 +523,11 @@ def sample_tokens(logits, temperature=1.0, top_k=None, *, u=None, seed=None, pos
     from .decode import _no_grad
     _no_grad(logits)
     assert logits.dim() == 2, "sample_tokens: logits must be (B, V)"
+    R = int(rows_per_seq)
+    if R < 1 or logits.shape[0] % R:
+        raise ValueError(f"sample_tokens: rows_per_seq must be >= 1 and divide the {logits.shape[0]} rows, got {R}")
+    if R > 1 and history is not None:
+        raise ValueError("sample_tokens: history is not taken with rows_per_seq > 1")
     b = _gpu(logits)
     if b == "hip" and sample_tokens_eligible(logits):
         from .decode import sample_params, sample_tokens_hip
@@ -462,13 +535,13 @@ def sample_tokens(logits, temperature=1.0, top_k=None, *, u=None, seed=None, pos
             params = sample_params(temperature, top_k, logits.device)
         if u is None and seed is not None and not isinstance(seed, torch.Tensor):
             seed = torch.tensor([_wrap_i64(seed)], dtype=torch.int64).to(logits.device)
-        return sample_tokens_hip(logits, params, u, seed, positions, out, history, u_out)
+        return sample_tokens_hip(logits, params, u, seed, positions, out, history, u_out, R, position_offset)
     if params is not None:
         from .decode import read_sample_params
         temperature, top_k = read_sample_params(params)
     if u is None:
         assert seed is not None and positions is not None, "sample_tokens: without u, seed and positions are needed"
-        u = ref.philox_uniform(seed, positions)
+        u = ref.philox_uniform(seed, positions, R, position_offset)
     if u_out is not None:
         u_out.copy_(u)
     return ref.sample_tokens(logits, temperature, top_k, u, None, positions, out, history,
@@ -511,7 +584,8 @@ __all__ = [
     "attention_qkv", "linear_attention_qkv", "attention", "rope_attention_packed", "linear_rope_attention",
     "cross_entropy", "swiglu_mlp", "linear_residual_layer_norm", "mlp_residual_layer_norm",
     "linear_residual_rms_norm", "swiglu_residual_rms_norm",
-    "linear_cross_entropy", "attention_decode", "kv_append", "linear_decode", "linear_decode_eligible",
+    "linear_cross_entropy", "attention_decode", "attention_decode_multi", "spec_draft", "spec_accept",
+    "kv_append", "linear_decode", "linear_decode_eligible",
     "sample_tokens", "sample_tokens_eligible", "Fp8Weight", "quantize_fp8", "quantize_kv_fp8",
 ]
 

@@ -138,12 +138,63 @@ def read_sample_params(params):
     return struct.unpack("<f", struct.pack("<i", bits))[0], (k if k > 0 else None)
 
 
-def sample_tokens_hip(logits, params, u=None, seed=None, positions=None, out=None, history=None, u_out=None):
+def sample_tokens_hip(logits, params, u=None, seed=None, positions=None, out=None, history=None, u_out=None,
+                      rows_per_seq=1, position_offset=0):
     """One launch, one workgroup per row: the token of every row of logits (B, V) -> (B, 1) int64
     (``out`` when given).  ``params`` from :func:`sample_params`; ``u`` (B,) fp32 or the kernel's
-    own Philox draw from ``seed`` (1,) int64 and ``positions`` (B,) int32, all on the device."""
+    own Philox draw from ``seed`` (1,) int64 and ``positions`` (B,) int32, all on the device
+    (``positions`` (B / R,) with ``rows_per_seq`` = R rows per sequence)."""
     _no_grad(logits)
-    return C().sample_tokens(logits, params, u, seed, positions, out, history, u_out).view(-1, 1)
+    if rows_per_seq == 1 and position_offset == 0:
+        return C().sample_tokens(logits, params, u, seed, positions, out, history, u_out).view(-1, 1)
+    return C().sample_tokens(logits, params, u, seed, positions, out, history, u_out, int(rows_per_seq),
+                             int(position_offset)).view(-1, 1)
+
+
+def attention_decode_multi_hip(q, k_cache, v_cache, kv_lens, scale=None, splits=0):
+    """q (B, Tq, Hq, D) with Tq <= 16, caches (B, Tmax, Hkv, D), kv_lens (B,) int32 on the device
+    (the Tq new tokens included) -> (B, Tq, Hq, D): csrc/attn_decode_multi.hip, planned as
+    :func:`attention_decode_hip` plans (``splits = 0``: from Tmax)."""
+    _no_grad(q, k_cache, v_cache)
+    scale = 1.0 / math.sqrt(q.shape[-1]) if scale is None else float(scale)
+    return C().attn_decode_multi(q, k_cache, v_cache, kv_lens, scale, int(splits))
+
+
+def attention_decode_multi_torch(q, k_cache, v_cache, kv_lens, scale=None):
+    """Stock PyTorch: SDPA with an explicit mask on each row's valid slice (reads the lengths on
+    the host)."""
+    from .reference import decode_multi_bounds
+    _no_grad(q, k_cache, v_cache)
+    B, Tq, Hq, D = q.shape
+    Tmax, Hkv = k_cache.shape[1], k_cache.shape[2]
+    rep = Hq // Hkv
+    out = torch.zeros(B, Tq, Hq, D, dtype=q.dtype, device=q.device)
+    for b, n in enumerate(kv_lens.tolist()):
+        bounds = decode_multi_bounds(n, Tq, Tmax)
+        top = max(bounds)
+        if top == 0:
+            continue
+        k, v = k_cache[b, :top].transpose(0, 1), v_cache[b, :top].transpose(0, 1)  # (Hkv, top, D)
+        if rep > 1:
+            k, v = k.repeat_interleave(rep, 0), v.repeat_interleave(rep, 0)
+        lim = torch.tensor(bounds, device=q.device).view(Tq, 1)
+        mask = torch.arange(top, device=q.device).view(1, top) < lim  # (Tq, top)
+        y = torch.nn.functional.scaled_dot_product_attention(
+            q[b].transpose(0, 1)[None], k[None], v[None], attn_mask=mask, scale=scale)[0]  # (Hq, Tq, D)
+        y = y.transpose(0, 1).masked_fill(~mask.any(1).view(Tq, 1, 1), 0.0)  # a query without keys is zeros
+        out[b] = y
+    return out
+
+
+def spec_draft_hip(history, cur, out, ngram):
+    """One launch (csrc/spec_decode.hip): see ``ops.spec_draft``."""
+    C().spec_draft(history, cur, out, int(ngram))
+    return out
+
+
+def spec_accept_hip(tokens, target, start, lens, stop, history):
+    """One launch (csrc/spec_decode.hip): see ``ops.spec_accept``."""
+    C().spec_accept(tokens, target, start, lens, stop, history)
 
 
 def attention_decode_torch(q, k_cache, v_cache, kv_lens, scale=None, k_scale=None, v_scale=None):

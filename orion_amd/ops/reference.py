@@ -140,6 +140,89 @@ def attention_decode(q, k_cache, v_cache, kv_lens, scale=None, k_scale=None, v_s
     return out.to(q.dtype)
 
 
+def decode_multi_bounds(n, Tq, Tmax):
+    """The key bounds of the Tq queries of a row of length n (the Tq new tokens included):
+    query t attends keys [0, clamp(n - Tq + 1 + t, 0, min(n, Tmax)))."""
+    top = max(0, min(int(n), Tmax))
+    return [max(0, min(int(n) - Tq + 1 + t, top)) for t in range(Tq)]
+
+
+def attention_decode_multi(q, k_cache, v_cache, kv_lens, scale=None):
+    """A few queries per row against a key/value cache with a causal tail: q (B, Tq, Hq, D), caches
+    (B, Tmax, Hkv, D), kv_lens (B,) including the Tq tokens of the forward in progress ->
+    (B, Tq, Hq, D).  Query t of row b attends keys [0, lim), lim as in :func:`decode_multi_bounds`;
+    a query without keys is zeros and nothing at or beyond min(kv_lens[b], Tmax) is read.  fp32
+    math, returned in q's dtype; bf16 caches only."""
+    if k_cache.dtype == torch.float8_e4m3fn or v_cache.dtype == torch.float8_e4m3fn:
+        raise ValueError("attention_decode_multi takes bf16 caches only, not float8_e4m3fn")
+    B, Tq, Hq, D = q.shape
+    Tmax, Hkv = k_cache.shape[1], k_cache.shape[2]
+    rep = Hq // Hkv
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    out = torch.zeros(B, Tq, Hq, D, dtype=torch.float32, device=q.device)
+    for b, n in enumerate(kv_lens.tolist()):
+        bounds = decode_multi_bounds(n, Tq, Tmax)
+        top = max(bounds)
+        if top == 0:
+            continue
+        kf = k_cache[b, :top].float().repeat_interleave(rep, dim=1).transpose(0, 1)  # (Hq, top, D)
+        vf = v_cache[b, :top].float().repeat_interleave(rep, dim=1).transpose(0, 1)
+        for t, lim in enumerate(bounds):
+            if lim == 0:
+                continue
+            s = torch.einsum("hd,hnd->hn", q[b, t].float(), kf[:, :lim]) * scale
+            out[b, t] = torch.einsum("hn,hnd->hd", s.softmax(-1), vf[:, :lim])
+    return out.to(q.dtype)
+
+
+def spec_draft(history, cur, out, ngram):
+    """The n-gram draft of a speculative step, in plain Python: history (B, L) int64 with columns
+    [0, cur[b]] known, out (B, k + 1) int64.  out[b, 0] = history[b, cur]; with g = ngram and j the
+    largest index in [0, cur - g] whose g tokens equal the row's last g, P = cur - g + 1 - j and
+    draft i (1..k) = history[b, j + g + ((i - 1) mod P)]: the continuation of the latest earlier
+    occurrence, periodic once it runs into the present.  Without a match (or cur < g) every draft
+    is history[b, cur]."""
+    g = int(ngram)
+    assert g >= 1, "ngram must be >= 1"
+    L = history.shape[1]
+    rows, curs = history.tolist(), cur.tolist()
+    for b, h in enumerate(rows):
+        c = max(0, min(int(curs[b]), L - 1))
+        tail = c - g + 1
+        j = -1
+        for cand in range(tail - 1, -1, -1):
+            if h[cand:cand + g] == h[tail:tail + g]:
+                j = cand
+                break
+        vals = [h[c]] + [h[c] if j < 0 else h[j + g + (i - 1) % (tail - j)] for i in range(1, out.shape[1])]
+        out[b] = torch.tensor(vals, dtype=out.dtype)
+    return out
+
+
+def spec_accept(tokens, target, start, lens, stop, history):
+    """The accept rule of a speculative step, in plain Python: tokens (B, k + 1) the current token
+    then the drafts, target (B, k + 1) the draws from the logits of each input.  a = the number of
+    leading i in 1..k with tokens[b, i] == target[b, i - 1]; e = clamp(min(a + 1, stop[b] -
+    start[b]), 0, k + 1); history[b, start[b] + 1 + i] = target[b, i] for i < e (columns >= L
+    skipped) and lens[b] = start[b] + e.  Returns the list of e."""
+    k = tokens.shape[1] - 1
+    L = history.shape[1]
+    tok, tgt, st, sp = tokens.tolist(), target.tolist(), start.tolist(), stop.tolist()
+    es = []
+    for b in range(len(tok)):
+        a = 0
+        while a < k and tok[b][a + 1] == tgt[b][a]:
+            a += 1
+        e = max(0, min(a + 1, int(sp[b]) - int(st[b]), k + 1))
+        for i in range(e):
+            col = int(st[b]) + 1 + i
+            if 0 <= col < L:
+                history[b, col] = tgt[b][i]
+        lens[b] = int(st[b]) + e
+        es.append(e)
+    return es
+
+
 def kv_append(k_new, v_new, k_cache, v_cache, kv_lens, q=None, cos=None, sin=None, k_scale=None, v_scale=None):
     """Write k_new / v_new (B, T, Hkv, D) into the caches (B, Tmax, Hkv, D) at positions
     kv_lens[b] + t; positions >= Tmax are skipped.  With tables k is rotated at its position
@@ -228,18 +311,22 @@ def uniform_from_word(x0):
     return np.minimum(u + np.float32(2.0 ** -25), np.float32(1.0 - 2.0 ** -24))
 
 
-def philox_uniform(seed, positions):
+def philox_uniform(seed, positions, rows_per_seq=1, position_offset=0):
     """The sampling kernel's uniforms, bit for bit: row b draws word 0 of Philox4x32-10 with the
     two 32-bit halves of the 64-bit ``seed`` (an int or a one-element tensor) as key and
     (positions[b], b, 0, 0) as counter; u = :func:`uniform_from_word` of it, strictly inside (0, 1).
-    ``positions`` (B,) integer tensor -> (B,) fp32 on its device."""
+    ``positions`` (B,) integer tensor -> (B,) fp32 on its device.  With ``rows_per_seq`` = R the
+    result is (B R,): row r = b R + t draws from (positions[b] + position_offset + t, b, 0, 0)."""
     import numpy as np
     seed = int(seed.reshape(-1)[0].item()) if isinstance(seed, torch.Tensor) else int(seed)
     seed &= (1 << 64) - 1
+    R = int(rows_per_seq)
     pos = positions.detach().cpu().numpy().astype(np.int64)
+    seq = np.repeat(np.arange(pos.shape[0]), R)
+    pos = np.repeat(pos, R) + int(position_offset) + np.tile(np.arange(R), pos.shape[0])
     ctr = np.zeros((pos.shape[0], 4), dtype=np.int64)
     ctr[:, 0] = pos & 0xFFFFFFFF
-    ctr[:, 1] = np.arange(pos.shape[0])
+    ctr[:, 1] = seq
     x0 = philox4x32_10(ctr, (seed & 0xFFFFFFFF, seed >> 32))[:, 0]
     return torch.from_numpy(uniform_from_word(x0)).to(positions.device)
 
@@ -266,16 +353,20 @@ def sample_cdf(logits, temperature=1.0, top_k=None, dtype=torch.float64):
 
 
 def sample_tokens(logits, temperature=1.0, top_k=None, u=None, seed=None, positions=None, out=None, history=None,
-                  dtype=torch.float64):
+                  dtype=torch.float64, rows_per_seq=1, position_offset=0):
     """The models' sampling rule with an explicit uniform per row: the token of row b is the first
     kept index whose running sum (:func:`sample_cdf`, fp64) exceeds u[b] Z, or the last kept
     index if rounding leaves none.  ``u`` (B,) is given or is :func:`philox_uniform` of ``seed``
-    and ``positions``.  Returns (B, 1) int64 (``out`` (B,) or (B, 1) when given); with ``history``
-    (B, L) the token also goes to history[b, positions[b]] unless the position is >= L."""
+    and ``positions`` (with ``rows_per_seq`` = R and ``position_offset``: row r of the (B R, V)
+    logits is token r % R of sequence r // R, positions stays (B,) and history is refused).
+    Returns (B, 1) int64 (``out`` (B,) or (B, 1) when given); with ``history`` (B, L) the token
+    also goes to history[b, positions[b]] unless the position is >= L."""
     B, V = logits.shape
+    if rows_per_seq != 1 and history is not None:
+        raise ValueError("sample_tokens: history is not taken with rows_per_seq > 1")
     if u is None:
         assert seed is not None and positions is not None, "without u, seed and positions are needed"
-        u = philox_uniform(seed, positions)
+        u = philox_uniform(seed, positions, rows_per_seq, position_offset)
     c, Z = sample_cdf(logits, temperature, top_k, dtype)
     tok = torch.searchsorted(c, u.to(device=c.device, dtype=dtype).view(B, 1) * Z, right=True)
     keep = sample_keep_mask(logits, top_k)

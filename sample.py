@@ -15,7 +15,10 @@ torch ops between the steps (``generate(..., sampler="device")``).  ``--decode_w
 ``fused`` or ``graph``) decodes from per-row FP8 (e4m3) copies of the projection weights, quantised
 once per sample (``generate(..., weights="fp8")``).  ``--decode_kv=fp8`` (with any ``--kv_cache``)
 keeps the key/value cache as FP8 (e4m3) bytes with one scale per token and head
-(``generate(..., kv="fp8")``): about half the cache's memory.
+(``generate(..., kv="fp8")``): about half the cache's memory.  ``--speculative=K --ngram=G`` (with
+``--kv_cache=fused`` or ``graph`` and ``--sampler=device``) verifies K tokens guessed from the
+latest earlier occurrence of the last G tokens in one decode step and keeps those that equal the
+sampler's own draws (``generate(..., speculative=K, ngram=G)``): the same tokens in fewer steps.
 """
 from __future__ import annotations
 
@@ -29,7 +32,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 DEFAULTS = dict(out_dir="out", start="\n", num_samples=10, max_new_tokens=500, temperature=0.8,
                 top_k=200, seed=1337, device="cuda", ckpt="ckpt.pt", kv_cache=False, sampler="torch",
-                decode_weights="bf16", decode_kv="bf16")
+                decode_weights="bf16", decode_kv="bf16", speculative=None, ngram=3)
 
 
 def main(argv=None):
@@ -72,10 +75,12 @@ def main(argv=None):
     kv = cfg["kv_cache"]
     with torch.no_grad():
         for _ in range(cfg["num_samples"]):
-            # generate() rejects a --kv_cache, --sampler, --decode_weights or --decode_kv it does not know
+            # generate() rejects a --kv_cache, --sampler, --decode_weights, --decode_kv or --speculative it
+            # does not know or cannot combine
             y = model.generate(x, cfg["max_new_tokens"], temperature=cfg["temperature"], top_k=cfg["top_k"],
                                use_cache=kv if isinstance(kv, str) else bool(kv), sampler=cfg["sampler"],
-                               weights=cfg["decode_weights"], kv=cfg["decode_kv"])
+                               weights=cfg["decode_weights"], kv=cfg["decode_kv"], speculative=cfg["speculative"],
+                               ngram=cfg["ngram"])
             toks = y[0].tolist()
             print(decode(toks) if decode else toks)
             print("---------------")

@@ -11,7 +11,14 @@ alternating; (iii) the skinny decode linear (csrc/linear_decode.hip)
 and its FP8-weight form (csrc/linear_decode_fp8.hip) at every projection shape of ``gpt2`` and of
 the Llama-2-7B layer at M = 1, 8, 16 beside the same call through ``F.linear`` with its separate
 norm / activation / residual launches; (iv) the sampling kernel (csrc/sample.hip) beside ``sample_logits`` (stock
-torch ops) on the same logits at B 1, 8, 16 and V 50,304 and 32,000, top-k 200 and none.
+torch ops) on the same logits at B 1, 8, 16 and V 50,304 and 32,000, top-k 200 and none;
+(v) the multi-query decode kernel (csrc/attn_decode_multi.hip) at Tq 4 and 8 beside Tq single-query
+calls on the shapes of (i) (``--multi``); (vi) speculative decoding (``--speculative``): generated
+tokens/s of ``gpt2`` at B 1 with k 3 and 7 guesses per step beside the plain
+``use_cache="graph", sampler="device"`` session, the arms alternating, in three drafting regimes:
+all-correct drafts (a ``draft=`` tensor holding the plain run's tokens: the ceiling), all-wrong
+drafts (the price of a verify step) and n-gram drafts on a periodic prompt, with the mean tokens
+per verify step of each.
 
 The kernel timing rotates over enough distinct caches to exceed the 256 MB Infinity Cache, so
 every call streams its K and V from HBM; bytes/s counts the K + V actually read (one pass per
@@ -21,7 +28,7 @@ counts the weight bytes (the FP8 arm's: one per element and four per row).
 Prints one JSON line per measurement.
 
 usage: python scripts/bench_decode.py [--shapes a,b] [--kernel 0|1] [--linear 0|1] [--sample 0|1] [--generate 0|1]
-                                      [--rounds N]
+                                      [--multi 0|1] [--speculative 0|1] [--rounds N]
 """
 import argparse
 import json
@@ -108,6 +115,37 @@ def bench_kernel(name, B, Hq, Hkv, D, T, rounds):
     res["hip_over_copy_rate"] = round(res["hip_TBs"] / HBM_COPY_TBS, 3)
     res["fp8_over_copy_rate"] = round(res["fp8_TBs"] / HBM_COPY_TBS, 3)
     res["fp8_over_hip"] = round(us["hip"] / us["fp8"], 2)  # > 1: the FP8 kernel is faster than the bf16 one
+    print(json.dumps(res), flush=True)
+
+
+def bench_kernel_multi(name, B, Hq, Hkv, D, T, Tq, rounds):
+    """One ``ops.attention_decode_multi`` over Tq queries per row beside the Tq single-query calls
+    it is bit-equal to, rotating over caches as :func:`bench_kernel` does."""
+    g = torch.Generator(device="cuda").manual_seed(0)
+    kv_bytes = 2 * B * T * Hkv * D * 2
+    n_buf = max(2, math.ceil(512e6 / kv_bytes))
+    caches = [torch.randn(2, B, T, Hkv, D, device="cuda", generator=g).to(torch.bfloat16) for _ in range(n_buf)]
+    q = torch.randn(B, Tq, Hq, D, device="cuda", generator=g).to(torch.bfloat16)
+    lens = torch.full((B,), T, dtype=torch.int32, device="cuda")
+    lens_t = [lens - (Tq - 1 - t) for t in range(Tq)]
+
+    def multi(i):
+        c = caches[i % n_buf]
+        return ops.attention_decode_multi(q, c[0], c[1], lens)
+
+    def singles(i):
+        c = caches[i % n_buf]
+        return [ops.attention_decode(q[:, t], c[0], c[1], lens_t[t]) for t in range(Tq)]
+
+    assert torch.equal(multi(0), torch.stack(singles(0), dim=1))
+    us = _time_us({"multi": multi, "singles": singles}, rounds)
+    res = dict(bench="decode_kernel_multi", shape=name, B=B, Hq=Hq, Hkv=Hkv, D=D, len=T, Tq=Tq,
+               kv_mbytes=round(kv_bytes / 1e6, 1), rotating_caches=n_buf, hbm_copy_TBs=HBM_COPY_TBS)
+    for k, v in us.items():
+        res[f"{k}_us"] = round(v, 2)
+    res["multi_TBs"] = round(kv_bytes / us["multi"] / 1e6, 3)  # one pass over K and V
+    res["multi_over_one_single"] = round(us["multi"] / (us["singles"] / Tq), 2)
+    res["singles_over_multi"] = round(us["singles"] / us["multi"], 2)
     print(json.dumps(res), flush=True)
 
 
@@ -272,6 +310,58 @@ def bench_generate(B, prompt_len, new_tokens, rounds):
     print(json.dumps(res), flush=True)
 
 
+def bench_speculative(k, prompt_len, new_tokens, rounds, top_k=200):
+    """``gpt2`` (random init) at B 1: the plain captured session beside speculative sessions with k
+    guesses per step, every session built and captured before the timed rounds; each timed run
+    is reset + prefill + the whole sampling loop under one seed, so all arms emit the same
+    tokens.  Tokens/s are medians over alternating rounds; ``*_tok_per_step`` is the mean number
+    of tokens a verify step emitted."""
+    torch.manual_seed(0)
+    model = build_gpt2("gpt2").to("cuda").to(torch.bfloat16).eval()
+    g = torch.Generator().manual_seed(1)
+    prompts = {"random": torch.randint(0, 50257, (1, prompt_len), generator=g).to("cuda"),
+               "periodic": torch.randint(0, 50257, (1, 8), generator=g).repeat(1, prompt_len // 8).to("cuda")}
+    max_len = prompt_len + new_tokens - 1
+
+    def run(sess, prompt):
+        sess.reset()
+        torch.manual_seed(7)
+        return sess.generate(prompt, new_tokens, 0.8, top_k)
+
+    plain = model.decode_session(1, max_len, graph=True, sampler="device")
+    want = {name: run(plain, p) for name, p in prompts.items()}
+    arms = {"plain": (plain, "random"), "plain_periodic": (plain, "periodic")}
+    for name, draft in (("all_correct", want["random"]), ("all_wrong", (want["random"] + 1) % 50257)):
+        arms[name] = (model.decode_session(1, max_len, graph=True, sampler="device", speculative=k, draft=draft),
+                      "random")
+    arms["ngram_periodic"] = (model.decode_session(1, max_len, graph=True, sampler="device", speculative=k),
+                              "periodic")
+    for name, (sess, pname) in arms.items():  # warm-up and capture; the tokens are the plain loop's
+        assert torch.equal(run(sess, prompts[pname]), want[pname]), name
+    torch.cuda.synchronize()
+    ts = {name: [] for name in arms}
+    for _ in range(rounds):
+        for name, (sess, pname) in arms.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run(sess, prompts[pname])
+            torch.cuda.synchronize()
+            ts[name].append(time.perf_counter() - t0)
+    res = dict(bench="speculative", model="gpt2", B=1, k=k, prompt=prompt_len, new_tokens=new_tokens, top_k=top_k,
+               temperature=0.8, rounds=rounds)
+    med = {name: sorted(v)[len(v) // 2] for name, v in ts.items()}
+    for name, v in med.items():
+        res[f"{name}_tok_per_s"] = round(new_tokens / v, 1)
+        res[f"{name}_spread"] = round((max(ts[name]) - min(ts[name])) / v, 3)
+        sess = arms[name][0]
+        if sess.speculative is not None:
+            res[f"{name}_tok_per_step"] = round(sess.spec_emitted / sess.spec_steps, 2)
+    res["all_correct_over_plain"] = round(med["plain"] / med["all_correct"], 2)
+    res["all_wrong_over_plain"] = round(med["plain"] / med["all_wrong"], 2)
+    res["ngram_periodic_over_plain_periodic"] = round(med["plain_periodic"] / med["ngram_periodic"], 2)
+    print(json.dumps(res), flush=True)
+
+
 def bench_weight_bytes():
     """Bytes of projection weight a decode session holds, bf16 beside fp8: ``gpt2`` from real
     sessions (with the relative logit error of the fp8 session's prefill against the unquantised
@@ -300,6 +390,8 @@ def main():
     ap.add_argument("--linear", type=int, default=1)
     ap.add_argument("--sample", type=int, default=1)
     ap.add_argument("--generate", type=int, default=1)
+    ap.add_argument("--multi", type=int, default=1)
+    ap.add_argument("--speculative", type=int, default=1)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--shapes", default=",".join(SHAPES), help="decode-kernel shapes, comma-separated")
     a = ap.parse_args()
@@ -310,6 +402,10 @@ def main():
         if a.kernel:
             for name in a.shapes.split(","):
                 bench_kernel(name, rounds=max(a.rounds, 5) * 2, **SHAPES[name])
+        if a.multi:
+            for name in a.shapes.split(","):
+                for Tq in (4, 8):
+                    bench_kernel_multi(name, Tq=Tq, rounds=max(a.rounds, 5) * 2, **SHAPES[name])
         if a.linear:
             for model, shapes in LINEAR_SHAPES.items():
                 for shape in shapes:
@@ -325,6 +421,10 @@ def main():
             for B in (1, 8):
                 bench_generate(B, 64, 256, a.rounds)
             bench_generate(8, 768, 256, a.rounds)  # a long context: where re-running the prefix costs
+        if a.speculative:
+            for k in (3, 7):
+                bench_speculative(k, 64, 256, max(a.rounds, 5))
+            bench_speculative(7, 64, 256, max(a.rounds, 5), top_k=1)  # greedy: a random-init model repeats itself
 
 
 if __name__ == "__main__":
