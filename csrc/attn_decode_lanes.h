@@ -1,6 +1,6 @@
-// Lane-level helpers of the decode attention kernels (csrc/attn_decode.hip on a bf16 cache,
-// csrc/attn_decode_fp8.hip on an FP8 one): a key row of D elements is spread 8 elements per lane
-// over an aligned group of D / 8 = 8 or 16 lanes.
+// Lane-level helpers of the decode attention kernel (csrc/attn_decode_core.h) and the cache appends
+// (csrc/attn_decode.hip), on a bf16 or an FP8 cache: a key row of D elements is spread 8 elements per
+// lane over an aligned group of D / 8 = 8 or 16 lanes.
 #pragma once
 
 #include "common.h"
@@ -63,5 +63,50 @@ ORION_DEVICE float lanes_max(float v) {
 }
 
 ORION_DEVICE float finite_or_zero(float m) { return m == -INFINITY ? 0.f : m; }
+
+// The cache appends' thread mapping: element i is group pg of 8 rotation pairs (the lower and the
+// upper 8 elements at pg * 8 and D / 2 + pg * 8) of head h, among the HT = Hq + 2 Hkv heads
+// q | k_new | v_new of token t of row b; the token lands at pos, and is skipped when !ok.
+struct AppendIndex {
+  int pg, h, t, b;
+  long pos;
+  bool ok;
+};
+
+ORION_DEVICE AppendIndex append_index(long i, int P8, int HT, int T, const int* kv_lens, int Tmax) {
+  AppendIndex x;
+  x.pg = (int)(i % P8);
+  const long row = i / P8;
+  x.h = (int)(row % HT);
+  x.t = (int)((row / HT) % T);
+  x.b = (int)(row / ((long)HT * T));
+  x.pos = (long)kv_lens[x.b] + x.t;
+  x.ok = x.pos >= 0 && x.pos < Tmax;
+  return x;
+}
+
+// A skipped token has no position to rotate at: its q row gets a defined value.
+ORION_DEVICE void append_zero_q(bf16_t* dst, int D, int pg) {
+  const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+  *reinterpret_cast<bf16x8*>(dst + pg * 8) = z;
+  *reinterpret_cast<bf16x8*>(dst + D / 2 + pg * 8) = z;
+}
+
+// The 8 pairs (lo[j], hi[j]) rotated in fp32 by row pos of the [npos][D / 2] tables; not rounded.
+ORION_DEVICE void rotate_pairs(const float* cosv, const float* sinv, long pos, int D, int pg, bf16x8 lo, bf16x8 hi,
+                               float (&y1)[8], float (&y2)[8]) {
+  const float* cr = cosv + pos * (D / 2) + pg * 8;
+  const float* sr = sinv + pos * (D / 2) + pg * 8;
+  const f32x4 c0 = *reinterpret_cast<const f32x4*>(cr), c1 = *reinterpret_cast<const f32x4*>(cr + 4);
+  const f32x4 s0 = *reinterpret_cast<const f32x4*>(sr), s1 = *reinterpret_cast<const f32x4*>(sr + 4);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float cc = j < 4 ? c0[j] : c1[j - 4];
+    const float ss = j < 4 ? s0[j] : s1[j - 4];
+    const float x1 = bf2f(lo[j]), x2 = bf2f(hi[j]);
+    y1[j] = x1 * cc - x2 * ss;
+    y2[j] = x2 * cc + x1 * ss;
+  }
+}
 
 }  // namespace orion

@@ -1001,31 +1001,33 @@ void check_cache_inputs(const Tensor& k_cache, const Tensor& v_cache, const Tens
   TORCH_CHECK(k_cache.device() == v_cache.device() && k_cache.device() == kv_lens.device(), "device mismatch");
 }
 
-// What attn_decode and attn_decode_fp8 share: the checks on q and splits, the split plan (`plan`: the
-// kernel's own) with its workspace (kept alive by ws_o / ws_ml), and every field of the parameter
-// block P but the scales.  The caller holds the device guard.  Returns o.
-template <class P, class Plan>
-Tensor attn_decode_args(P& p, Plan plan, const Tensor& q, const Tensor& k_cache, const Tensor& v_cache,
-                        const Tensor& kv_lens, double scale, int64_t splits, Tensor& ws_o, Tensor& ws_ml) {
+// What the three decode attention ops share: the checks on q and splits, the split plan with its
+// workspace (kept alive by ws_o / ws_ml), and every field of the parameter block but the scales.
+// q is (B, Tq, Hq, D) (`multi`) or (B, Hq, D), taken as Tq = 1; returns o in q's shape.  The caller
+// holds the device guard.
+Tensor attn_decode_args(orion::DecodeParams& p, bool multi, const Tensor& q, const Tensor& k_cache,
+                        const Tensor& v_cache, const Tensor& kv_lens, double scale, int64_t splits, Tensor& ws_o,
+                        Tensor& ws_ml) {
   check_bf16(q, "q");
-  TORCH_CHECK(q.dim() == 3 && q.size(0) == k_cache.size(0) && q.size(2) == k_cache.size(3),
-              "q must be (B, Hq, D) matching the cache");
-  TORCH_CHECK(q.size(1) > 0 && q.size(1) % k_cache.size(2) == 0, "Hq must be a multiple of Hkv");
+  TORCH_CHECK(q.dim() == (multi ? 4 : 3) && q.size(0) == k_cache.size(0) && q.size(-1) == k_cache.size(3),
+              "q must be ", multi ? "(B, Tq, Hq, D)" : "(B, Hq, D)", " matching the cache");
+  const Tensor q4 = multi ? q : q.unsqueeze(1);
+  TORCH_CHECK(q4.size(1) >= 1 && q4.size(1) <= 16, "Tq must be in [1, 16], got ", q4.size(1));
+  TORCH_CHECK(q4.size(2) > 0 && q4.size(2) % k_cache.size(2) == 0, "Hq must be a multiple of Hkv");
   TORCH_CHECK(q.device() == k_cache.device(), "device mismatch");
   TORCH_CHECK(splits >= 0 && splits <= 1024, "splits must be in [0, 1024]");
-  check_rows16(q, "q");
-  const int D = q.size(2);
-  p.B = q.size(0); p.Hq = q.size(1); p.Hkv = k_cache.size(2); p.Tmax = k_cache.size(1);
-  p.splits = plan(p.B, p.Hkv, p.Tmax, D, (int)splits, &p.chunk);
-  auto o = at::empty({p.B, p.Hq, D}, q.options());
+  check_rows16(q4, "q");
+  const int D = q4.size(3);
+  p.B = q4.size(0); p.Tq = q4.size(1); p.Hq = q4.size(2); p.Hkv = k_cache.size(2); p.Tmax = k_cache.size(1);
+  p.splits = orion_attn_decode_plan(p.B, p.Hkv, p.Tmax, D, (int)splits, &p.chunk);
+  auto o = at::empty(q.sizes(), q.options());
   if (p.splits > 1) {
-    ws_o = at::empty({p.B, p.Hq, p.splits, D}, q.options().dtype(at::kFloat));
-    ws_ml = at::empty({p.B, p.Hq, p.splits, 2}, q.options().dtype(at::kFloat));
+    ws_o = at::empty({p.B, p.Tq, p.Hq, p.splits, D}, q.options().dtype(at::kFloat));
+    ws_ml = at::empty({p.B, p.Tq, p.Hq, p.splits, 2}, q.options().dtype(at::kFloat));
     p.ws_o = ws_o.data_ptr<float>();
     p.ws_ml = ws_ml.data_ptr<float>();
   }
-  p.q = (const unsigned short*)q.data_ptr();
-  p.q_sb = q.stride(0); p.q_sh = q.stride(1);
+  set_view(p.q, p.q_sb, p.q_st, p.q_sh, q4);
   set_view(p.k, p.k_sb, p.k_st, p.k_sh, k_cache);
   set_view(p.v, p.v_sb, p.v_st, p.v_sh, v_cache);
   p.o = (unsigned short*)o.data_ptr();
@@ -1042,8 +1044,8 @@ Tensor attn_decode(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache
   c10::hip::HIPGuardMasqueradingAsCUDA g(q.device());
   orion::DecodeParams p{};
   Tensor ws_o, ws_ml;
-  Tensor o = attn_decode_args(p, orion_attn_decode_plan, q, k_cache, v_cache, kv_lens, scale, splits, ws_o, ws_ml);
-  check_launch(orion_attn_decode(p, (int)q.size(2), cur_stream()), "attn_decode");
+  Tensor o = attn_decode_args(p, false, q, k_cache, v_cache, kv_lens, scale, splits, ws_o, ws_ml);
+  check_launch(orion_attn_decode(p, (int)q.size(-1), cur_stream()), "attn_decode");
   return o;
 }
 
@@ -1052,43 +1054,19 @@ Tensor attn_decode(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache
 Tensor attn_decode_multi(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& kv_lens,
                          double scale, int64_t splits) {
   check_cache_inputs(k_cache, v_cache, kv_lens);
-  check_bf16(q, "q");
-  TORCH_CHECK(q.dim() == 4 && q.size(0) == k_cache.size(0) && q.size(3) == k_cache.size(3),
-              "q must be (B, Tq, Hq, D) matching the cache");
-  TORCH_CHECK(q.size(1) >= 1 && q.size(1) <= 16, "Tq must be in [1, 16], got ", q.size(1));
-  TORCH_CHECK(q.size(2) > 0 && q.size(2) % k_cache.size(2) == 0, "Hq must be a multiple of Hkv");
-  TORCH_CHECK(q.device() == k_cache.device(), "device mismatch");
-  TORCH_CHECK(splits >= 0 && splits <= 1024, "splits must be in [0, 1024]");
-  check_rows16(q, "q");
   c10::hip::HIPGuardMasqueradingAsCUDA g(q.device());
-  orion::DecodeMultiParams p{};
-  const int D = q.size(3);
-  p.B = q.size(0); p.Tq = q.size(1); p.Hq = q.size(2); p.Hkv = k_cache.size(2); p.Tmax = k_cache.size(1);
-  p.splits = orion_attn_decode_plan(p.B, p.Hkv, p.Tmax, D, (int)splits, &p.chunk);
-  auto o = at::empty({p.B, p.Tq, p.Hq, D}, q.options());
+  orion::DecodeParams p{};
   Tensor ws_o, ws_ml;
-  if (p.splits > 1) {
-    ws_o = at::empty({p.B, p.Tq, p.Hq, p.splits, D}, q.options().dtype(at::kFloat));
-    ws_ml = at::empty({p.B, p.Tq, p.Hq, p.splits, 2}, q.options().dtype(at::kFloat));
-    p.ws_o = ws_o.data_ptr<float>();
-    p.ws_ml = ws_ml.data_ptr<float>();
-  }
-  set_view(p.q, p.q_sb, p.q_st, p.q_sh, q);
-  set_view(p.k, p.k_sb, p.k_st, p.k_sh, k_cache);
-  set_view(p.v, p.v_sb, p.v_st, p.v_sh, v_cache);
-  p.o = (unsigned short*)o.data_ptr();
-  p.kv_lens = kv_lens.data_ptr<int>();
-  p.scale_log2 = (float)(scale * LOG2E);
-  check_launch(orion_attn_decode_multi(p, D, cur_stream()), "attn_decode_multi");
+  Tensor o = attn_decode_args(p, true, q, k_cache, v_cache, kv_lens, scale, splits, ws_o, ws_ml);
+  check_launch(orion_attn_decode_multi(p, (int)q.size(-1), cur_stream()), "attn_decode_multi");
   return o;
 }
 
 // What kv_append and kv_append_fp8 share: every check past the cache's own, and every field of the
-// parameter block P but the scales, the lengths and the caches' element type.  Returns the rotated q's
-// buffer (an empty tensor without q).
-template <class P>
-Tensor kv_append_args(P& p, const Tensor& k_new, const Tensor& v_new, const Tensor& k_cache, const Tensor& v_cache,
-                      const c10::optional<Tensor>& q, const c10::optional<Tensor>& cosv,
+// parameter block but the scales and the lengths.  Returns the rotated q's buffer (an empty tensor
+// without q).
+Tensor kv_append_args(orion::AppendParams& p, const Tensor& k_new, const Tensor& v_new, const Tensor& k_cache,
+                      const Tensor& v_cache, const c10::optional<Tensor>& q, const c10::optional<Tensor>& cosv,
                       const c10::optional<Tensor>& sinv) {
   check_bf16(k_new, "k_new"); check_bf16(v_new, "v_new");
   TORCH_CHECK(k_new.dim() == 4 && k_new.sizes() == v_new.sizes() && k_new.size(0) == k_cache.size(0) &&
@@ -1146,7 +1124,7 @@ Tensor kv_append(const Tensor& k_new, const Tensor& v_new, Tensor k_cache, Tenso
   return q_out;
 }
 
-// ------------------------------------------------------------------ FP8 key/value cache (csrc/attn_decode_fp8.hip)
+// ------------------------------------------------------------------ FP8 key/value cache (csrc/attn_decode.hip)
 // e4m3 bytes (B, Tmax, Hkv, D) with unit stride on D and 8-byte aligned rows; fp32 scales
 // (B, Hkv, Tmax) with unit stride on the tokens
 void check_fp8_cache_inputs(const Tensor& k_cache, const Tensor& v_cache, const Tensor& k_scale,
@@ -1179,13 +1157,12 @@ Tensor attn_decode_fp8(const Tensor& q, const Tensor& k_cache, const Tensor& v_c
                        const Tensor& v_scale, const Tensor& kv_lens, double scale, int64_t splits) {
   check_fp8_cache_inputs(k_cache, v_cache, k_scale, v_scale, kv_lens);
   c10::hip::HIPGuardMasqueradingAsCUDA g(q.device());
-  orion::DecodeFp8Params p{};
+  orion::DecodeParams p{};
   Tensor ws_o, ws_ml;
-  Tensor o = attn_decode_args(p, orion_attn_decode_fp8_plan, q, k_cache, v_cache, kv_lens, scale, splits, ws_o,
-                              ws_ml);
+  Tensor o = attn_decode_args(p, false, q, k_cache, v_cache, kv_lens, scale, splits, ws_o, ws_ml);
   p.k_scale = k_scale.data_ptr<float>(); p.ks_sb = k_scale.stride(0); p.ks_sh = k_scale.stride(1);
   p.v_scale = v_scale.data_ptr<float>(); p.vs_sb = v_scale.stride(0); p.vs_sh = v_scale.stride(1);
-  check_launch(orion_attn_decode_fp8(p, (int)q.size(2), cur_stream()), "attn_decode_fp8");
+  check_launch(orion_attn_decode_fp8(p, (int)q.size(-1), cur_stream()), "attn_decode_fp8");
   return o;
 }
 
@@ -1196,7 +1173,7 @@ Tensor kv_append_fp8(const Tensor& k_new, const Tensor& v_new, Tensor k_cache, T
                      const c10::optional<Tensor>& cosv, const c10::optional<Tensor>& sinv) {
   check_fp8_cache_inputs(k_cache, v_cache, k_scale, v_scale, kv_lens);
   c10::hip::HIPGuardMasqueradingAsCUDA g(k_new.device());
-  orion::AppendFp8Params p{};
+  orion::AppendParams p{};
   Tensor q_out = kv_append_args(p, k_new, v_new, k_cache, v_cache, q, cosv, sinv);
   p.k_scale = k_scale.data_ptr<float>(); p.ks_sb = k_scale.stride(0); p.ks_sh = k_scale.stride(1);
   p.v_scale = v_scale.data_ptr<float>(); p.vs_sb = v_scale.stride(0); p.vs_sh = v_scale.stride(1);

@@ -1,5 +1,5 @@
 // OCP e4m3fn bytes <-> bf16 / fp32 in registers on gfx950, shared by csrc/linear_decode_fp8.hip and
-// csrc/attn_decode_fp8.hip.  Every e4m3 value is a bf16 (and an fp32) value, so the widening
+// csrc/attn_decode_core.h.  Every e4m3 value is a bf16 (and an fp32) value, so the widening
 // conversions are exact; the narrowing one rounds to nearest even and is only given values
 // already clamped to [-448, 448].
 #pragma once

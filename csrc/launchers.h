@@ -8,8 +8,6 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "attn_decode_fp8_params.h"
-#include "attn_decode_multi_params.h"
 #include "attn_decode_params.h"
 #include "attn_plan.h"
 #include "linear_decode_fp8_params.h"
@@ -112,24 +110,22 @@ int orion_lmhead_bwd_prep(const void* X, long ldx, int Cdim, long N, const int64
                           const float* invz, const float* inv_n, const float* g, float* srow, void* Xs,
                           int transposed, hipStream_t st);
 
-// attn_decode.hip, attn_decode_fp8.hip, attn_decode_multi.hip, linear_decode.hip, linear_decode_fp8.hip,
-// sample.hip, spec_decode.hip: generation
+// attn_decode.hip, linear_decode.hip, linear_decode_fp8.hip, sample.hip, spec_decode.hip: generation
 // (negative: a field of p failed its check)
 int orion_attn_decode_split_plan(int tile, int B, int Hkv, int Tmax, int splits, int* chunk);  // key tiles of `tile`
-int orion_attn_decode_plan(int B, int Hkv, int Tmax, int D, int splits, int* chunk);
+int orion_attn_decode_plan(int B, int Hkv, int Tmax, int D, int splits, int* chunk);  // of all three ops below
+// one query per row (Tq = 1) on a bf16 cache, on an FP8 cache (-6: no scales), and Tq <= 16 queries per row
+// with a causal tail on a bf16 cache (-2 also: a chunk that is no whole number of key tiles)
 int orion_attn_decode(const orion::DecodeParams& p, int D, hipStream_t st);
+int orion_attn_decode_fp8(const orion::DecodeParams& p, int D, hipStream_t st);
+int orion_attn_decode_multi(const orion::DecodeParams& p, int D, hipStream_t st);
 int orion_attn_decode_combine(const float* ws_o, const float* ws_ml, void* o, int splits, int D, long heads,
                               hipStream_t st);
 int orion_kv_append(const orion::AppendParams& p, hipStream_t st);
-int orion_attn_decode_fp8_tile(int D);  // keys per workgroup iteration of the FP8 kernel
-int orion_attn_decode_fp8_plan(int B, int Hkv, int Tmax, int D, int splits, int* chunk);
-int orion_attn_decode_fp8(const orion::DecodeFp8Params& p, int D, hipStream_t st);
-int orion_kv_append_fp8(const orion::AppendFp8Params& p, hipStream_t st);
+int orion_kv_append_fp8(const orion::AppendParams& p, hipStream_t st);  // -6: no scales
 int orion_linear_decode(const orion::LinearDecodeParams& p, hipStream_t st);
 int orion_linear_decode_fp8(const orion::LinearDecodeFp8Params& p, hipStream_t st);  // -1 also K % 16
 int orion_sample_tokens(const orion::SampleParams& p, hipStream_t st);
-// Tq <= 16 queries per row with a causal tail; splits / chunk from orion_attn_decode_plan (-2 also: another tile)
-int orion_attn_decode_multi(const orion::DecodeMultiParams& p, int D, hipStream_t st);
 // spec_decode.hip: out (B, k1) = the current token and k1 - 1 n-gram drafts; the accept rule of a verify step
 int orion_spec_draft(const long* history, long hist_rs, const int* cur, long* out, long out_rs, int B, int L,
                      int k1, int ngram, hipStream_t st);

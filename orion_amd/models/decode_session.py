@@ -74,7 +74,7 @@ class DecodeSession:
     model's own projection weights and the models are called exactly as without the keyword.
 
     ``kv="fp8"`` makes the cache a :class:`KVCache` with ``kv_dtype="fp8"``: the append quantises
-    each head row to e4m3 bytes with one fp32 scale (csrc/attn_decode_fp8.hip) and the decode
+    each head row to e4m3 bytes with one fp32 scale (csrc/attn_decode.hip) and the decode
     attention streams those bytes, (D + 4) / 2D of the bf16 cache's; ``cache_bytes`` is what the
     cache holds.  The step keeps its launches (the two cache ops change kernels), so a captured
     step stays one linear chain.  A prefill of more than one token attends the stored values of

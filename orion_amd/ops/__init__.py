@@ -333,7 +333,7 @@ def attention_decode(q, k_cache, v_cache, kv_lens, scale=None, splits=0, k_scale
     Tmax, so pass the cache cut at the host's bound of the length); inference only.
     ``float8_e4m3fn`` caches (:class:`KVCache` with ``kv_dtype="fp8"``) come with their fp32
     scales ``k_scale`` / ``v_scale`` (B, Hkv, Tmax), value = scale * byte, and run
-    csrc/attn_decode_fp8.hip; bf16 caches refuse scales."""
+    csrc/attn_decode.hip's FP8 kernel; bf16 caches refuse scales."""
     fp8 = ref.cache_is_fp8(k_cache, v_cache, k_scale, v_scale)
     b = _gpu(q)
     if b == "hip":
@@ -353,8 +353,8 @@ def attention_decode_multi(q, k_cache, v_cache, kv_lens, scale=None, splits=0):
     kv_lens (B,) int32 including the Tq tokens of the forward in progress -> (B, Tq, Hq, D).
     Query t of row b attends keys [0, lim), lim = clamp(kv_lens[b] - Tq + 1 + t, 0,
     min(kv_lens[b], Tmax)); a query with lim = 0 yields zeros and keys at or beyond
-    min(kv_lens[b], Tmax) are never loaded.  On the GPU one launch of csrc/attn_decode_multi.hip
-    (plus the combine of the key splits), whose output [:, t] equals bit for bit
+    min(kv_lens[b], Tmax) are never loaded.  On the GPU one launch of csrc/attn_decode.hip's
+    multi-query kernel (plus the combine of the key splits), whose output [:, t] equals bit for bit
     ``attention_decode(q[:, t], ..., kv_lens - (Tq - 1 - t), splits=splits)``: ``splits`` means
     what it means there (0: planned from Tmax).  An FP8 cache raises ``ValueError``.  Inference
     only."""

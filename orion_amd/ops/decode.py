@@ -1,4 +1,4 @@
-"""Generation-time ops over the HIP kernels of csrc/attn_decode.hip, csrc/attn_decode_fp8.hip,
+"""Generation-time ops over the HIP kernels of csrc/attn_decode.hip,
 csrc/linear_decode.hip and csrc/linear_decode_fp8.hip: single-query attention against a bf16 or
 FP8 key/value cache (split over keys, lengths read on the device), the cache append with optional
 RoPE (quantising into an FP8 cache), and the skinny (M <= 16) linear
@@ -90,8 +90,9 @@ def kv_append_hip(k_new, v_new, k_cache, v_cache, kv_lens, q=None, cos=None, sin
 
 
 def attention_decode_fp8_tile(D):
-    """Keys per workgroup iteration of csrc/attn_decode_fp8.hip (its ``DecodeFp8Shape<D>::TILE``:
-    4 waves x 4 loads x 64 / (D / 8) keys per wave-wide load); a split is a whole number of them."""
+    """Keys per workgroup iteration of the decode attention kernel on either cache type
+    (csrc/attn_decode_core.h's ``DecodeShape<D>::TILE``: 4 waves x 4 loads x 64 / (D / 8) keys per
+    wave-wide load); a split is a whole number of them."""
     return 4 * 4 * (64 // (D // 8))
 
 
@@ -153,7 +154,7 @@ def sample_tokens_hip(logits, params, u=None, seed=None, positions=None, out=Non
 
 def attention_decode_multi_hip(q, k_cache, v_cache, kv_lens, scale=None, splits=0):
     """q (B, Tq, Hq, D) with Tq <= 16, caches (B, Tmax, Hkv, D), kv_lens (B,) int32 on the device
-    (the Tq new tokens included) -> (B, Tq, Hq, D): csrc/attn_decode_multi.hip, planned as
+    (the Tq new tokens included) -> (B, Tq, Hq, D): the multi-query kernel of csrc/attn_decode.hip, planned as
     :func:`attention_decode_hip` plans (``splits = 0``: from Tmax)."""
     _no_grad(q, k_cache, v_cache)
     scale = 1.0 / math.sqrt(q.shape[-1]) if scale is None else float(scale)

@@ -5,7 +5,7 @@ registers and applies the row scale once, in its fp32 epilogue.
 
 The key/value cache uses the same bytes with one fp32 scale per (token, KV head) row of ``D``
 values: :func:`quantize_kv_fp8` is the one definition of that rule, followed by the cache append
-of csrc/attn_decode_fp8.hip and by ``ops.reference.kv_append``."""
+of csrc/attn_decode.hip and by ``ops.reference.kv_append``."""
 from __future__ import annotations
 
 from dataclasses import dataclass

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Generation benchmark: (i) the split-KV decode attention kernel (csrc/attn_decode.hip) beside
-torch SDPA on the same cache view and beside its FP8-cache form (csrc/attn_decode_fp8.hip) on the
+torch SDPA on the same cache view and beside its FP8-cache form (the same file) on the
 quantised caches, at the GPT-2, the Llama-GQA and the Llama-2-7B MHA decode shapes; (ii) generated
 tokens/s of ``gpt2`` with and without the KV cache (prompt 64 + 256 new tokens at B 1 and 8, and
 a long-context point, prompt 768 at B 8) and on the fused decode step, eager (``fused``) and
@@ -12,7 +12,7 @@ and its FP8-weight form (csrc/linear_decode_fp8.hip) at every projection shape o
 the Llama-2-7B layer at M = 1, 8, 16 beside the same call through ``F.linear`` with its separate
 norm / activation / residual launches; (iv) the sampling kernel (csrc/sample.hip) beside ``sample_logits`` (stock
 torch ops) on the same logits at B 1, 8, 16 and V 50,304 and 32,000, top-k 200 and none;
-(v) the multi-query decode kernel (csrc/attn_decode_multi.hip) at Tq 4 and 8 beside Tq single-query
+(v) the multi-query decode kernel (csrc/attn_decode.hip) at Tq 4 and 8 beside Tq single-query
 calls on the shapes of (i) (``--multi``); (vi) speculative decoding (``--speculative``): generated
 tokens/s of ``gpt2`` at B 1 with k 3 and 7 guesses per step beside the plain
 ``use_cache="graph", sampler="device"`` session, the arms alternating, in three drafting regimes:

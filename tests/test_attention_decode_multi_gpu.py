@@ -1,4 +1,4 @@
-"""Multi-query decode attention (csrc/attn_decode_multi.hip) on the GPU: bit-equality with the
+"""Multi-query decode attention (csrc/attn_decode.hip) on the GPU: bit-equality with the
 single-query kernel per query, the bf16 budget against the fp32 reference, NaN beyond the
 lengths, determinism and the refusal of an FP8 cache.
 

@@ -1,4 +1,4 @@
-"""The FP8 key/value cache kernels of csrc/attn_decode_fp8.hip on the GPU: single-query attention
+"""The FP8 key/value cache kernels of csrc/attn_decode.hip on the GPU: single-query attention
 over e4m3 bytes with per-(token, head) scales and the quantising append.  Attention is held to the
 budget of tests/tolerance.py against the fp32 reference on the exactly dequantised cache (the
 baseline: SDPA in bf16 on that cache rounded to bf16), so only the kernel's own arithmetic is
@@ -88,6 +88,27 @@ def test_one_hot_selection_is_bit_exact(D, splits):
     for g in (4, 8):  # reversed inside each word / each lane's 8 bytes
         jr = (j // g) * g + (g - 1 - j % g)
         assert not torch.equal(kc.one_hot_expected(c, jr), want)
+
+
+@pytest.mark.parametrize("splits", [1, 3])
+@pytest.mark.parametrize("Hq,Hkv", [(2, 2), (8, 1), (16, 1)])  # 1 row, one full pass of 8, two passes
+@pytest.mark.parametrize("D", [64, 128])
+def test_unit_scale_fp8_cache_equals_the_bf16_kernel(D, Hq, Hkv, splits):
+    """The two cache types run one kernel body: e4m3 values are bf16 values, so on the widened cache
+    the bf16 kernel sees the same K and V, and (d * 1) * scale and fma(p * 1, v, acc) are its own
+    operations."""
+    tmax, tile = 384, attention_decode_fp8_tile(D)
+    g = torch.Generator().manual_seed(D + Hq)
+    q = torch.randn(2, Hq, D, generator=g).to(torch.bfloat16).to(DEV)
+    k8 = torch.randn(2, tmax, Hkv, D, generator=g).to(torch.float8_e4m3fn).to(DEV)
+    v8 = torch.randn(2, tmax, Hkv, D, generator=g).to(torch.float8_e4m3fn).to(DEV)
+    assert torch.equal(k8.to(torch.bfloat16).float(), k8.float())  # the widening is exact
+    lens = torch.tensor([tile + 3, 37], dtype=torch.int32, device=DEV)
+    one = torch.ones(2, Hkv, tmax, device=DEV)
+    want = ops.attention_decode(q, k8.to(torch.bfloat16), v8.to(torch.bfloat16), lens, splits=splits)
+    got = ops.attention_decode(q, k8, v8, lens, splits=splits, k_scale=one, v_scale=one)
+    assert torch.isfinite(want).all() and want.abs().max() > 0
+    assert torch.equal(got, want), f"{(got.float() - want.float()).abs().max().item()} off"
 
 
 @pytest.mark.parametrize("D,Hq,Hkv", [(64, 4, 4), (128, 8, 2)])
