@@ -1184,14 +1184,15 @@ Tensor kv_append_fp8(const Tensor& k_new, const Tensor& v_new, Tensor k_cache, T
 
 // ------------------------------------------------------------------ decode linear (csrc/linear_decode.hip)
 // What the bf16 and the FP8 op share: every check but the weight's dtype, and every field of the
-// parameter block P but the weight's.  K must be a multiple of `kmult`; returns y.
+// parameter block P but the weight's.  K must be a multiple of `kmult`; a column of w holds `kpack`
+// elements of K (2 for MXFP4 code pairs); returns y.
 template <class P>
-Tensor linear_decode_args(P& p, const char* op, int64_t kmult, const Tensor& x, const Tensor& w,
+Tensor linear_decode_args(P& p, const char* op, int64_t kmult, int64_t kpack, const Tensor& x, const Tensor& w,
                           const c10::optional<Tensor>& bias, int64_t norm, const c10::optional<Tensor>& norm_w,
                           const c10::optional<Tensor>& norm_b, double eps, int64_t act,
                           const c10::optional<Tensor>& residual, const c10::optional<Tensor>& out) {
   check_bf16(x, "x");
-  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == w.size(1), op, ": x (M, K) and weight (N, K), got ",
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == w.size(1) * kpack, op, ": x (M, K) and weight (N, K), got ",
               x.sizes(), " and ", w.sizes());
   const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
   TORCH_CHECK(M >= 1 && M <= 16, op, ": 1 <= M <= 16 rows, got ", M);
@@ -1262,7 +1263,7 @@ Tensor linear_decode(const Tensor& x, const Tensor& w, const c10::optional<Tenso
                      int64_t act, const c10::optional<Tensor>& residual, c10::optional<Tensor> out) {
   check_bf16(x, "x"); check_bf16(w, "weight");
   orion::LinearDecodeParams p{};
-  Tensor y = linear_decode_args(p, "linear_decode", 8, x, w, bias, norm, norm_w, norm_b, eps, act, residual, out);
+  Tensor y = linear_decode_args(p, "linear_decode", 8, 1, x, w, bias, norm, norm_w, norm_b, eps, act, residual, out);
   p.w = (const unsigned short*)w.data_ptr();
   check_launch(orion_linear_decode(p, cur_stream()), "linear_decode");
   return y;
@@ -1279,13 +1280,39 @@ Tensor linear_decode_fp8(const Tensor& x, const Tensor& wq, const Tensor& w_scal
   TORCH_CHECK(wq.scalar_type() == at::kFloat8_e4m3fn, "linear_decode_fp8: weight must be Float8_e4m3fn (OCP e4m3, ",
               "the gfx950 format), got ", wq.scalar_type());
   orion::LinearDecodeFp8Params p{};
-  Tensor y = linear_decode_args(p, "linear_decode_fp8", 16, x, wq, bias, norm, norm_w, norm_b, eps, act, residual, out);
+  Tensor y = linear_decode_args(p, "linear_decode_fp8", 16, 1, x, wq, bias, norm, norm_w, norm_b, eps, act, residual, out);
   TORCH_CHECK(w_scale.is_cuda() && w_scale.device() == x.device() && w_scale.scalar_type() == at::kFloat &&
                   w_scale.dim() == 1 && w_scale.size(0) == wq.size(0) && w_scale.is_contiguous(),
               "linear_decode_fp8: w_scale must be a contiguous float32 vector of ", wq.size(0), " on x's device");
   p.wq = (const unsigned char*)wq.data_ptr();
   p.w_scale = w_scale.data_ptr<float>();
   check_launch(orion_linear_decode_fp8(p, cur_stream()), "linear_decode_fp8");
+  return y;
+}
+
+// ------------------------------------------------------------------ MXFP4 decode linear (csrc/linear_decode_mxfp4.hip)
+// linear_decode with the weight as OCP MXFP4: wq (N, K / 2) uint8, two e2m1 codes per byte (even k in
+// the low nibble), and w_scale (N, K / 32) uint8 e8m0, W[n, k] = 2^(w_scale[n, k / 32] - 127) e2m1(code);
+// x, bias, the norm vectors, residual and out stay bf16.
+Tensor linear_decode_mxfp4(const Tensor& x, const Tensor& wq, const Tensor& w_scale,
+                           const c10::optional<Tensor>& bias, int64_t norm, const c10::optional<Tensor>& norm_w,
+                           const c10::optional<Tensor>& norm_b, double eps, int64_t act,
+                           const c10::optional<Tensor>& residual, c10::optional<Tensor> out) {
+  check_bf16(x, "x");
+  TORCH_CHECK(wq.is_cuda(), "weight must be a GPU tensor");
+  TORCH_CHECK(wq.scalar_type() == at::kByte, "linear_decode_mxfp4: weight must be uint8 (two e2m1 codes per byte), got ",
+              wq.scalar_type());
+  orion::LinearDecodeMxfp4Params p{};
+  Tensor y = linear_decode_args(p, "linear_decode_mxfp4", 32, 2, x, wq, bias, norm, norm_w, norm_b, eps, act,
+                                residual, out);
+  TORCH_CHECK(w_scale.is_cuda() && w_scale.device() == x.device() && w_scale.scalar_type() == at::kByte &&
+                  w_scale.dim() == 2 && w_scale.size(0) == wq.size(0) && w_scale.size(1) == x.size(1) / 32 &&
+                  w_scale.is_contiguous(),
+              "linear_decode_mxfp4: w_scale must be a contiguous uint8 (", wq.size(0), ", ", x.size(1) / 32,
+              ") tensor of e8m0 bytes on x's device");
+  p.wq = (const unsigned char*)wq.data_ptr();
+  p.w_scale = (const unsigned char*)w_scale.data_ptr();
+  check_launch(orion_linear_decode_mxfp4(p, cur_stream()), "linear_decode_mxfp4");
   return y;
 }
 
@@ -1466,6 +1493,7 @@ TORCH_LIBRARY(orion_amd, m) {
   m.def("kv_append_fp8(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor(c!) k_scale, Tensor(d!) v_scale, Tensor kv_lens, Tensor? q=None, Tensor? cos=None, Tensor? sin=None) -> Tensor");
   m.def("linear_decode(Tensor x, Tensor w, Tensor? bias, int norm, Tensor? norm_w, Tensor? norm_b, float eps, int act, Tensor? residual, Tensor(a!)? out=None) -> Tensor");
   m.def("linear_decode_fp8(Tensor x, Tensor wq, Tensor w_scale, Tensor? bias, int norm, Tensor? norm_w, Tensor? norm_b, float eps, int act, Tensor? residual, Tensor(a!)? out=None) -> Tensor");
+  m.def("linear_decode_mxfp4(Tensor x, Tensor wq, Tensor w_scale, Tensor? bias, int norm, Tensor? norm_w, Tensor? norm_b, float eps, int act, Tensor? residual, Tensor(a!)? out=None) -> Tensor");
   m.def("sample_tokens(Tensor logits, Tensor params, Tensor? u, Tensor? seed, Tensor? positions, Tensor(a!)? out=None, Tensor(b!)? history=None, Tensor(c!)? u_out=None, int rows_per_seq=1, int position_offset=0) -> Tensor");
   m.def("spec_draft(Tensor history, Tensor cur, Tensor(a!) out, int ngram) -> ()");
   m.def("spec_accept(Tensor tokens, Tensor target, Tensor start, Tensor(a!) lens, Tensor stop, Tensor(b!) history) -> ()");
@@ -1512,6 +1540,7 @@ TORCH_LIBRARY_IMPL(orion_amd, CUDA, m) {
   m.impl("kv_append_fp8", &kv_append_fp8);
   m.impl("linear_decode", &linear_decode);
   m.impl("linear_decode_fp8", &linear_decode_fp8);
+  m.impl("linear_decode_mxfp4", &linear_decode_mxfp4);
   m.impl("sample_tokens", &sample_tokens);
   m.impl("attn_decode_multi", &attn_decode_multi);
   m.impl("spec_draft", &spec_draft);

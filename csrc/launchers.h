@@ -11,6 +11,7 @@
 #include "attn_decode_params.h"
 #include "attn_plan.h"
 #include "linear_decode_fp8_params.h"
+#include "linear_decode_mxfp4_params.h"
 #include "linear_decode_params.h"
 #include "sample_params.h"
 
@@ -110,7 +111,8 @@ int orion_lmhead_bwd_prep(const void* X, long ldx, int Cdim, long N, const int64
                           const float* invz, const float* inv_n, const float* g, float* srow, void* Xs,
                           int transposed, hipStream_t st);
 
-// attn_decode.hip, linear_decode.hip, linear_decode_fp8.hip, sample.hip, spec_decode.hip: generation
+// attn_decode.hip, linear_decode.hip, linear_decode_fp8.hip, linear_decode_mxfp4.hip, sample.hip,
+// spec_decode.hip: generation
 // (negative: a field of p failed its check)
 int orion_attn_decode_split_plan(int tile, int B, int Hkv, int Tmax, int splits, int* chunk);  // key tiles of `tile`
 int orion_attn_decode_plan(int B, int Hkv, int Tmax, int D, int splits, int* chunk);  // of all three ops below
@@ -125,6 +127,7 @@ int orion_kv_append(const orion::AppendParams& p, hipStream_t st);
 int orion_kv_append_fp8(const orion::AppendParams& p, hipStream_t st);  // -6: no scales
 int orion_linear_decode(const orion::LinearDecodeParams& p, hipStream_t st);
 int orion_linear_decode_fp8(const orion::LinearDecodeFp8Params& p, hipStream_t st);  // -1 also K % 16
+int orion_linear_decode_mxfp4(const orion::LinearDecodeMxfp4Params& p, hipStream_t st);  // -1 also K % 32
 int orion_sample_tokens(const orion::SampleParams& p, hipStream_t st);
 // spec_decode.hip: out (B, k1) = the current token and k1 - 1 n-gram drafts; the accept rule of a verify step
 int orion_spec_draft(const long* history, long hist_rs, const int* cur, long* out, long out_rs, int B, int L,

@@ -1,4 +1,5 @@
-// Device helpers shared by csrc/linear_decode.hip and csrc/linear_decode_fp8.hip.
+// Device helpers shared by csrc/linear_decode.hip, csrc/linear_decode_fp8.hip and
+// csrc/linear_decode_mxfp4.hip.
 #pragma once
 
 #include "common.h"

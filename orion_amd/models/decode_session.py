@@ -70,8 +70,12 @@ class DecodeSession:
     on their dequantised values, so the prompt and the generated tokens see one model.  The
     model's parameters are not modified and the embedding tables stay as they are (GPT-2's tied
     ``wte`` is quantised as the head only); activations, the cache, attention and sampling do
-    not change.  With the default ``"bf16"``, ``qweights`` is None, ``weight_bytes`` counts the
-    model's own projection weights and the models are called exactly as without the keyword.
+    not change.  ``weights="mxfp4"`` does the same with ``ops.quantize_mxfp4`` (OCP MXFP4: e2m1
+    codes, one e8m0 scale per 32 along K, 4.25 bits per weight; ``qweights`` holds
+    ``ops.Mxfp4Weight`` and the step runs csrc/linear_decode_mxfp4.hip); every projection then
+    needs K % 32 == 0, checked at construction.  With the default ``"bf16"``, ``qweights`` is
+    None, ``weight_bytes`` counts the model's own projection weights and the models are called
+    exactly as without the keyword.
 
     ``kv="fp8"`` makes the cache a :class:`KVCache` with ``kv_dtype="fp8"``: the append quantises
     each head row to e4m3 bytes with one fp32 scale (csrc/attn_decode.hip) and the decode
@@ -104,8 +108,8 @@ class DecodeSession:
                  speculative=None, ngram=3, draft="ngram"):
         if sampler not in ("torch", "device"):
             raise ValueError(f"sampler must be 'torch' or 'device', got {sampler!r}")
-        if weights not in ("bf16", "fp8"):
-            raise ValueError(f"weights must be 'bf16' or 'fp8', got {weights!r}")
+        if weights not in ("bf16", "fp8", "mxfp4"):
+            raise ValueError(f"weights must be 'bf16', 'fp8' or 'mxfp4', got {weights!r}")
         if kv not in ("bf16", "fp8"):
             raise ValueError(f"kv must be 'bf16' or 'fp8', got {kv!r}")
         check_speculative(speculative, ngram, draft, batch, sampler, kv)
@@ -120,6 +124,13 @@ class DecodeSession:
         projections = list(model.decode_projections())
         if weights == "fp8":
             self.qweights = {name: ops.quantize_fp8(pw) for name, pw in projections}
+            projections = list(self.qweights.items())
+        elif weights == "mxfp4":
+            for name, pw in projections:  # the format's own condition, with or without a graph
+                if pw.shape[1] % 32:
+                    raise ValueError(f"DecodeSession(weights='mxfp4', graph={self.graph}): {name} {tuple(pw.shape)} "
+                                     "needs K % 32 == 0, one block scale per 32 elements of K")
+            self.qweights = {name: ops.quantize_mxfp4(pw) for name, pw in projections}
             projections = list(self.qweights.items())
         self.weight_bytes = sum(pw.nbytes for _, pw in projections)
         # what the model's calls get beyond their usual arguments: nothing for a bf16 session
@@ -136,8 +147,9 @@ class DecodeSession:
                 if K not in probes:
                     probes[K] = torch.empty(rows, K, device=w.device, dtype=w.dtype)
                 if not ops.linear_decode_eligible(probes[K], pw):
-                    kind = (f"{pw.dtype}", "K % 8 == 0") if self.qweights is None else \
-                        ("fp8 (e4m3, bf16 activations)", "K % 16 == 0")
+                    kind = {"bf16": (f"{getattr(pw, 'dtype', None)}", "K % 8 == 0"),
+                            "fp8": ("fp8 (e4m3, bf16 activations)", "K % 16 == 0"),
+                            "mxfp4": ("mxfp4 (e2m1, bf16 activations)", "K % 32 == 0")}[weights]
                     raise ValueError(f"DecodeSession(graph=True): {name} {tuple(pw.shape)} {kind[0]} is not "
                                      f"eligible for ops.linear_decode (bf16 on the HIP backend, {kind[1]}, "
                                      "contiguous weight), and a library GEMM must not be captured")

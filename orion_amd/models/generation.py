@@ -8,22 +8,21 @@ from __future__ import annotations
 
 import torch
 
-from ..ops.fp8 import Fp8Weight
-
 
 def session_weights(model, weights):
     """The weights of ``model.decode_projections()`` in that order, each replaced by the entry of
-    the mapping ``weights`` (name -> ``ops.Fp8Weight``) that carries its name; None without a
-    mapping, and the caller then reads the parameters as it always did."""
+    the mapping ``weights`` (name -> ``ops.Fp8Weight`` or ``ops.Mxfp4Weight``) that carries its
+    name; None without a mapping, and the caller then reads the parameters as it always did."""
     if weights is None:
         return None
     return [weights.get(name, p) for name, p in model.decode_projections()]
 
 
 def dense(weight, dtype):
-    """A weight that the plain ops take: an ``ops.Fp8Weight`` dequantised to ``dtype`` (a transient),
-    anything else as it is."""
-    return weight.dequant(dtype) if isinstance(weight, Fp8Weight) else weight
+    """A weight that the plain ops take: a quantised one (anything with ``dequant``: an
+    ``ops.Fp8Weight``, an ``ops.Mxfp4Weight``) dequantised to ``dtype`` (a transient), anything
+    else as it is."""
+    return weight.dequant(dtype) if hasattr(weight, "dequant") else weight
 
 
 def sample_logits(logits, temperature=1.0, top_k=None):
@@ -43,7 +42,8 @@ class Generation:
                        speculative=None, ngram=3, draft="ngram"):
         """A :class:`DecodeSession` for this model: the fused decode step, captured when ``graph``;
         ``sampler="device"`` draws the tokens with ``ops.sample_tokens`` inside that step,
-        ``weights="fp8"`` decodes from per-row e4m3 copies of the projection weights and
+        ``weights="fp8"`` decodes from per-row e4m3 copies of the projection weights,
+        ``weights="mxfp4"`` from MXFP4 copies (e2m1 codes, one e8m0 scale per 32 along K), and
         ``kv="fp8"`` keeps the key/value cache as e4m3 bytes with one scale per (token, KV head).
         ``speculative=k`` verifies k guessed tokens per step (``draft="ngram"`` with ``ngram``, or a
         (batch, L) tensor of guesses by position) and emits the plain loop's tokens."""
@@ -66,8 +66,10 @@ class Generation:
         the session's tokens with ``ops.sample_tokens`` inside the step (seeded from torch's
         default generator) instead of stock torch ops between the steps, and ``weights="fp8"``
         makes the session quantise the projection weights once (``ops.quantize_fp8``) and run the
-        prompt and every cached token on them.  The sliding-window loop beyond the context limit
-        keeps using the model's own (unquantised) weights, as it keeps clear of the session.
+        prompt and every cached token on them; ``weights="mxfp4"`` does so with
+        ``ops.quantize_mxfp4`` (4.25 bits per weight, every projection's K % 32 == 0).  The
+        sliding-window loop beyond the context limit keeps using the model's own (unquantised)
+        weights, as it keeps clear of the session.
         ``kv="fp8"`` (with ``use_cache`` True, ``"fused"`` or ``"graph"``) keeps the cache as e4m3
         bytes with one fp32 scale per (token, KV head): about half the cache's memory and bytes per
         step; the sliding-window loop has no cache and does not change.
@@ -86,10 +88,10 @@ class Generation:
         if sampler == "device" and not fused:
             raise ValueError("sampler='device' samples inside the fused decode step: use_cache must be 'fused' "
                              f"or 'graph', got {use_cache!r}")
-        if weights not in ("bf16", "fp8"):
-            raise ValueError(f"weights must be 'bf16' or 'fp8', got {weights!r}")
-        if weights == "fp8" and not fused:
-            raise ValueError("weights='fp8' decodes through the fused decode step: use_cache must be 'fused' "
+        if weights not in ("bf16", "fp8", "mxfp4"):
+            raise ValueError(f"weights must be 'bf16', 'fp8' or 'mxfp4', got {weights!r}")
+        if weights != "bf16" and not fused:
+            raise ValueError(f"weights='{weights}' decodes through the fused decode step: use_cache must be 'fused' "
                              f"or 'graph', got {use_cache!r}")
         if kv not in ("bf16", "fp8"):
             raise ValueError(f"kv must be 'bf16' or 'fp8', got {kv!r}")

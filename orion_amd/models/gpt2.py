@@ -221,7 +221,8 @@ class GPT(nn.Module, Generation):
         already in ``cache``; appends this call's keys / values.  T > 1 is a (chunked) prefill
         through the flash forward, T == 1 a decode step through ``ops.attention_decode``.  Plain
         ops throughout: the training-time fused residual sites have no place at M = B.
-        ``weights`` maps names of :meth:`decode_projections` to ``ops.Fp8Weight``: such a
+        ``weights`` maps names of :meth:`decode_projections` to quantised weights (anything with
+        ``dequant``: ``ops.Fp8Weight``, ``ops.Mxfp4Weight``): such a
         projection runs on its dequantised weight, one transient at a time (the embedding tables
         stay the model's).  An FP8 ``cache`` (``new_cache(kv_dtype="fp8")``) takes the
         appended keys / values quantised with their scales, and a T > 1 call attends the stored
@@ -272,7 +273,8 @@ class GPT(nn.Module, Generation):
         the logits of ``tokens`` (B, 1) at position ``cache.start`` go into ``logits_out``.  Every
         projection is one ``ops.linear_decode`` with the norm in its prologue and the bias /
         GELU / residual in its epilogue; the session has advanced ``cache.start`` / ``cache.lens``.
-        A projection named in ``weights`` (name -> ``ops.Fp8Weight``) streams that weight.
+        A projection named in ``weights`` (name -> ``ops.Fp8Weight`` or ``ops.Mxfp4Weight``) streams
+        that weight.
 
         ``tokens`` (B, Tq) with B Tq <= 16 is a speculative verify step: token t of row b sits at
         position ``cache.start[b] + t``, every projection runs on the B Tq rows, the Tq keys /

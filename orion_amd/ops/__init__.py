@@ -24,6 +24,7 @@ from .fp8 import Fp8Weight, quantize_fp8, quantize_kv_fp8
 # loaded here, before ``def linear`` below binds the name: the first import of a submodule
 # sets it as an attribute of the package, which later would replace the function
 from .linear import linear_hip
+from .mxfp4 import Mxfp4Weight, quantize_mxfp4
 
 _BACKEND = os.environ.get("ORION_AMD_OPS", "hip")
 
@@ -433,7 +434,8 @@ def linear_decode_eligible(x, weight):
     """Whether the skinny decode kernel (csrc/linear_decode.hip) takes this input on the HIP
     backend: bf16 GPU tensors, at most 16 rows of x with 16-byte aligned unit-stride rows,
     K % 8 == 0, a contiguous weight.  With an :class:`Fp8Weight`, whether the FP8 kernel
-    (csrc/linear_decode_fp8.hip) does: the same for bf16 x, with K % 16 == 0."""
+    (csrc/linear_decode_fp8.hip) does: the same for bf16 x, with K % 16 == 0; with an
+    :class:`Mxfp4Weight`, whether csrc/linear_decode_mxfp4.hip does: K % 32 == 0."""
     if not x.is_cuda or _BACKEND != "hip":
         return False
     from .decode import linear_decode_eligible as ok
@@ -467,17 +469,18 @@ def linear_decode(x, weight, bias=None, *, norm=None, norm_weight=None, norm_bia
     rows), else the plain ops composed; ``out`` (rows, Nout) takes the result in place.
     ``weight`` may be an :class:`Fp8Weight`: an eligible input streams its bytes through the FP8
     kernel, any other (the CPU, the torch backend, 17 or more rows) takes the path it would take
-    with a plain weight, on ``weight.dequant(x.dtype)``.  Inference only."""
+    with a plain weight, on ``weight.dequant(x.dtype)``.  An :class:`Mxfp4Weight` likewise, through
+    the MXFP4 kernel.  Inference only."""
     assert norm in (None, "layer", "rms") and act in (None, "gelu", "swiglu"), (norm, act)
     assert (norm is None) == (norm_weight is None), "norm_weight comes with a norm"
     from .decode import _no_grad
-    fp8 = isinstance(weight, Fp8Weight)
-    _no_grad(x, None if fp8 else weight, bias, norm_weight, norm_bias, residual)
+    quantised = isinstance(weight, (Fp8Weight, Mxfp4Weight))
+    _no_grad(x, None if quantised else weight, bias, norm_weight, norm_bias, residual)
     b = _gpu(x)
     if b == "hip" and linear_decode_eligible(x, weight):
         from .decode import linear_decode_hip
         return linear_decode_hip(x, weight, bias, norm, norm_weight, norm_bias, eps, act, residual, out)
-    if fp8:
+    if quantised:
         weight = weight.dequant(x.dtype)
     if b is None:
         y = ref.linear_decode(x, weight, bias, norm, norm_weight, norm_bias, eps, act, residual)
@@ -587,6 +590,7 @@ __all__ = [
     "linear_cross_entropy", "attention_decode", "attention_decode_multi", "spec_draft", "spec_accept",
     "kv_append", "linear_decode", "linear_decode_eligible",
     "sample_tokens", "sample_tokens_eligible", "Fp8Weight", "quantize_fp8", "quantize_kv_fp8",
+    "Mxfp4Weight", "quantize_mxfp4",
 ]
 
 

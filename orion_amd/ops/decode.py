@@ -1,11 +1,11 @@
-"""Generation-time ops over the HIP kernels of csrc/attn_decode.hip,
-csrc/linear_decode.hip and csrc/linear_decode_fp8.hip: single-query attention against a bf16 or
-FP8 key/value cache (split over keys, lengths read on the device), the cache append with optional
-RoPE (quantising into an FP8 cache), and the skinny (M <= 16) linear
-layer with a fused norm prologue and bias / activation / residual epilogue, on a bf16 weight or
-an :class:`~orion_amd.ops.fp8.Fp8Weight`.  Inference only: there is no backward, and
-an input that requires grad while gradients are enabled is an error rather than a silently
-dropped graph."""
+"""Generation-time ops over the HIP kernels of csrc/attn_decode.hip, csrc/linear_decode.hip,
+csrc/linear_decode_fp8.hip and csrc/linear_decode_mxfp4.hip: single-query attention against a
+bf16 or FP8 key/value cache (split over keys, lengths read on the device), the cache append with
+optional RoPE (quantising into an FP8 cache), and the skinny (M <= 16) linear layer with a fused
+norm prologue and bias / activation / residual epilogue, on a bf16 weight, an
+:class:`~orion_amd.ops.fp8.Fp8Weight` or an :class:`~orion_amd.ops.mxfp4.Mxfp4Weight`.
+Inference only: there is no backward, and an input that requires grad while gradients are
+enabled is an error rather than a silently dropped graph."""
 from __future__ import annotations
 
 import math
@@ -14,6 +14,7 @@ import torch
 
 from ._ext import C
 from .fp8 import Fp8Weight, dequantize_kv_fp8
+from .mxfp4 import Mxfp4Weight
 
 
 def _no_grad(*tensors):
@@ -35,17 +36,19 @@ def linear_decode_eligible(x, weight):
     """Whether csrc/linear_decode.hip takes x (..., K) (at most 16 rows that flatten to a view with
     16-byte aligned, unit-stride rows) against weight (N, K): both bf16 on the GPU, K % 8 == 0,
     weight contiguous.  For an :class:`Fp8Weight`, whether csrc/linear_decode_fp8.hip does: the
-    same with K % 16 == 0."""
-    kmult = 8
+    same with K % 16 == 0.  For an :class:`Mxfp4Weight`, whether csrc/linear_decode_mxfp4.hip
+    does: K, taken from the weight's logical shape, % 32 == 0 and 16-byte aligned codes."""
+    kmult, K = 8, weight.shape[-1]
     if isinstance(weight, Fp8Weight):
         kmult, weight = 16, weight.q
+    elif isinstance(weight, Mxfp4Weight):
+        kmult, weight = 32, weight.q
     elif weight.dtype != torch.bfloat16:
         return False
     if not (x.is_cuda and weight.is_cuda and x.dtype == torch.bfloat16):
         return False
-    if weight.dim() != 2 or x.dim() < 1 or x.shape[-1] != weight.shape[1] or not weight.is_contiguous():
+    if weight.dim() != 2 or x.dim() < 1 or x.shape[-1] != K or not weight.is_contiguous():
         return False
-    K = weight.shape[1]
     if K < kmult or K % kmult or weight.data_ptr() % 16 or x.numel() == 0 or x.numel() // K > MAX_ROWS:
         return False
     try:
@@ -59,13 +62,17 @@ def linear_decode_hip(x, weight, bias=None, norm=None, norm_weight=None, norm_bi
                       residual=None, out=None):
     """One launch: act(norm(x) W^T + bias) + residual for x (..., K) of at most 16 rows -> (..., Nout);
     ``out`` (rows, Nout) receives the result in place (a static buffer of a captured step)."""
-    _no_grad(x, None if isinstance(weight, Fp8Weight) else weight, bias, norm_weight, norm_bias, residual)
+    quantised = isinstance(weight, (Fp8Weight, Mxfp4Weight))
+    _no_grad(x, None if quantised else weight, bias, norm_weight, norm_bias, residual)
     K = weight.shape[1]
     n_out = weight.shape[0] // 2 if act == "swiglu" else weight.shape[0]
     r2 = None if residual is None else residual.view(-1, n_out)
     if isinstance(weight, Fp8Weight):
         y = C().linear_decode_fp8(x.view(-1, K), weight.q, weight.scale, bias, NORMS[norm], norm_weight, norm_bias,
                                   float(eps), ACTS[act], r2, out)
+    elif isinstance(weight, Mxfp4Weight):
+        y = C().linear_decode_mxfp4(x.view(-1, K), weight.q, weight.scale, bias, NORMS[norm], norm_weight,
+                                    norm_bias, float(eps), ACTS[act], r2, out)
     else:
         y = C().linear_decode(x.view(-1, K), weight, bias, NORMS[norm], norm_weight, norm_bias, float(eps),
                               ACTS[act], r2, out)

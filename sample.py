@@ -13,7 +13,8 @@ captured HIP graph (``generate(use_cache="fused" / "graph")``).  ``--sampler=dev
 ``fused`` or ``graph``) draws the tokens with the sampling kernel inside that step instead of stock
 torch ops between the steps (``generate(..., sampler="device")``).  ``--decode_weights=fp8`` (with
 ``fused`` or ``graph``) decodes from per-row FP8 (e4m3) copies of the projection weights, quantised
-once per sample (``generate(..., weights="fp8")``).  ``--decode_kv=fp8`` (with any ``--kv_cache``)
+once per sample (``generate(..., weights="fp8")``); ``--decode_weights=mxfp4`` from MXFP4 copies
+(e2m1 codes, one e8m0 scale per 32 along K: 4.25 bits per weight).  ``--decode_kv=fp8`` (with any ``--kv_cache``)
 keeps the key/value cache as FP8 (e4m3) bytes with one scale per token and head
 (``generate(..., kv="fp8")``): about half the cache's memory.  ``--speculative=K --ngram=G`` (with
 ``--kv_cache=fused`` or ``graph`` and ``--sampler=device``) verifies K tokens guessed from the

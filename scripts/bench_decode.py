@@ -6,11 +6,12 @@ tokens/s of ``gpt2`` with and without the KV cache (prompt 64 + 256 new tokens a
 a long-context point, prompt 768 at B 8) and on the fused decode step, eager (``fused``) and
 replayed from one captured HIP graph (``graph``) and with the tokens drawn inside that graph
 (``graph_device``: ``sampler="device"``) and from FP8 weights (``graph_device_fp8``: also
-``weights="fp8"``) or an FP8 key/value cache (``graph_device_kvfp8``: ``kv="fp8"``), the arms
-alternating; (iii) the skinny decode linear (csrc/linear_decode.hip)
-and its FP8-weight form (csrc/linear_decode_fp8.hip) at every projection shape of ``gpt2`` and of
-the Llama-2-7B layer at M = 1, 8, 16 beside the same call through ``F.linear`` with its separate
-norm / activation / residual launches; (iv) the sampling kernel (csrc/sample.hip) beside ``sample_logits`` (stock
+``weights="fp8"``), MXFP4 weights (``graph_device_mxfp4``: ``weights="mxfp4"``) or an FP8 key/value
+cache (``graph_device_kvfp8``: ``kv="fp8"``), the arms alternating; (iii) the skinny decode linear
+(csrc/linear_decode.hip) and its FP8-weight and MXFP4-weight forms (csrc/linear_decode_fp8.hip,
+csrc/linear_decode_mxfp4.hip) at every projection shape of ``gpt2`` and of the Llama-2-7B layer
+at M = 1, 8, 16 beside the same call through ``F.linear`` with its separate norm / activation /
+residual launches; (iv) the sampling kernel (csrc/sample.hip) beside ``sample_logits`` (stock
 torch ops) on the same logits at B 1, 8, 16 and V 50,304 and 32,000, top-k 200 and none;
 (v) the multi-query decode kernel (csrc/attn_decode.hip) at Tq 4 and 8 beside Tq single-query
 calls on the shapes of (i) (``--multi``); (vi) speculative decoding (``--speculative``): generated
@@ -24,7 +25,8 @@ The kernel timing rotates over enough distinct caches to exceed the 256 MB Infin
 every call streams its K and V from HBM; bytes/s counts the K + V actually read (one pass per
 KV head; the FP8 arm's own bytes: one per element and four per (token, head) scale); the linear
 timing rotates over weights the same way (each arm over more than 512 MB of its own format) and
-counts the weight bytes (the FP8 arm's: one per element and four per row).
+counts the weight bytes (the FP8 arm's: one per element and four per row; the MXFP4 arm's: half a
+byte per element and one per 32 elements).
 Prints one JSON line per measurement.
 
 usage: python scripts/bench_decode.py [--shapes a,b] [--kernel 0|1] [--linear 0|1] [--sample 0|1] [--generate 0|1]
@@ -173,6 +175,9 @@ def bench_linear(model, name, N, K, norm, act, bias, residual, M, rounds):
     q_bytes = N * K + 4 * N
     n_q = max(2, math.ceil(512e6 / q_bytes))
     qs = [ops.quantize_fp8(ws[i] if i < n_buf else r(N, K)) for i in range(n_q)]
+    x_bytes = N * K // 2 + N * K // 32
+    n_x = max(2, math.ceil(512e6 / x_bytes))
+    xs = [ops.quantize_mxfp4(ws[i] if i < n_buf else r(N, K)) for i in range(n_x)]
     n_out = N // 2 if act == "swiglu" else N
     x, b, res = r(M, K), (r(N) if bias else None), (r(M, n_out) if residual else None)
     nw, nb = (r(K) if norm else None), (r(K) if norm == "layer" else None)
@@ -182,6 +187,9 @@ def bench_linear(model, name, N, K, norm, act, bias, residual, M, rounds):
 
     def fp8(i):
         return ops.linear_decode(x, qs[i % n_q], b, norm=norm, norm_weight=nw, norm_bias=nb, act=act, residual=res)
+
+    def mxfp4(i):
+        return ops.linear_decode(x, xs[i % n_x], b, norm=norm, norm_weight=nw, norm_bias=nb, act=act, residual=res)
 
     def stock(i):
         h = x
@@ -199,19 +207,24 @@ def bench_linear(model, name, N, K, norm, act, bias, residual, M, rounds):
         return y if res is None else y + res
 
     assert ops.linear_decode_eligible(x, ws[0]) and ops.linear_decode_eligible(x, qs[0])
+    assert ops.linear_decode_eligible(x, xs[0])
     err = (hip(0).float() - stock(0).float()).abs().max().item()
-    us = _time_us({"hip": hip, "fp8": fp8, "f_linear": stock}, rounds)
+    us = _time_us({"hip": hip, "fp8": fp8, "mxfp4": mxfp4, "f_linear": stock}, rounds)
     out = dict(bench="linear_decode", model=model, proj=name, M=M, N=N, K=K, norm=norm, act=act, bias=bias,
                residual=residual, w_mbytes=round(w_bytes / 1e6, 2), rotating_weights=n_buf,
                fp8_w_mbytes=round(q_bytes / 1e6, 2), fp8_rotating_weights=n_q,
+               mxfp4_w_mbytes=round(x_bytes / 1e6, 2), mxfp4_rotating_weights=n_x,
                max_abs_diff_vs_f_linear=round(err, 4), hbm_copy_TBs=HBM_COPY_TBS)
     for k, v in us.items():
         out[f"{k}_us"] = round(v, 2)
-        out[f"{k}_GBs"] = round((q_bytes if k == "fp8" else w_bytes) / v / 1e3, 1)
+        out[f"{k}_GBs"] = round({"fp8": q_bytes, "mxfp4": x_bytes}.get(k, w_bytes) / v / 1e3, 1)
     out["hip_over_copy_rate"] = round(out["hip_GBs"] / 1e3 / HBM_COPY_TBS, 3)
     out["fp8_over_copy_rate"] = round(out["fp8_GBs"] / 1e3 / HBM_COPY_TBS, 3)
     out["speedup"] = round(us["f_linear"] / us["hip"], 2)
     out["fp8_over_hip"] = round(us["hip"] / us["fp8"], 2)  # > 1: the FP8 kernel is faster than the bf16 one
+    out["mxfp4_over_copy_rate"] = round(out["mxfp4_GBs"] / 1e3 / HBM_COPY_TBS, 3)
+    out["mxfp4_over_hip"] = round(us["hip"] / us["mxfp4"], 2)  # > 1: the MXFP4 kernel is faster than the bf16 one
+    out["mxfp4_over_fp8"] = round(us["fp8"] / us["mxfp4"], 2)  # > 1: faster than the FP8 one
     print(json.dumps(out), flush=True)
 
 
@@ -276,6 +289,7 @@ def bench_generate(B, prompt_len, new_tokens, rounds):
     arms = {"cached": dict(use_cache=True), "uncached": dict(use_cache=False), "fused": dict(use_cache="fused"),
             "graph": dict(use_cache="graph"), "graph_device": dict(use_cache="graph", sampler="device"),
             "graph_device_fp8": dict(use_cache="graph", sampler="device", weights="fp8"),
+            "graph_device_mxfp4": dict(use_cache="graph", sampler="device", weights="mxfp4"),
             "graph_device_kvfp8": dict(use_cache="graph", sampler="device", kv="fp8")}
     for kw in arms.values():  # warm-up: every shape of every arm
         model.generate(prompt, new_tokens, top_k=200, **kw)
@@ -300,6 +314,7 @@ def bench_generate(B, prompt_len, new_tokens, rounds):
     res["graph_over_best_baseline"] = round(best / med["graph"], 2)
     res["graph_device_over_graph"] = round(med["graph"] / med["graph_device"], 2)
     res["graph_device_fp8_over_graph_device"] = round(med["graph_device"] / med["graph_device_fp8"], 2)
+    res["graph_device_mxfp4_over_graph_device"] = round(med["graph_device"] / med["graph_device_mxfp4"], 2)
     res["graph_device_kvfp8_over_graph_device"] = round(med["graph_device"] / med["graph_device_kvfp8"], 2)
     steady = bench_graph_steady(model, B, prompt_len, new_tokens)
     res["graph_steady_ms_per_token"] = round(steady["token"] * 1e3, 3)
@@ -307,6 +322,8 @@ def bench_generate(B, prompt_len, new_tokens, rounds):
     res["graph_sampling_ms_per_token"] = round((steady["token"] - steady["replay"]) * 1e3, 3)
     steady = bench_graph_steady(model, B, prompt_len, new_tokens, weights="fp8")
     res["graph_fp8_replay_ms_per_token"] = round(steady["replay"] * 1e3, 3)
+    steady = bench_graph_steady(model, B, prompt_len, new_tokens, weights="mxfp4")
+    res["graph_mxfp4_replay_ms_per_token"] = round(steady["replay"] * 1e3, 3)
     print(json.dumps(res), flush=True)
 
 
@@ -363,24 +380,28 @@ def bench_speculative(k, prompt_len, new_tokens, rounds, top_k=200):
 
 
 def bench_weight_bytes():
-    """Bytes of projection weight a decode session holds, bf16 beside fp8: ``gpt2`` from real
-    sessions (with the relative logit error of the fp8 session's prefill against the unquantised
-    model, random init), the Llama-2-7B shape from its projection shapes alone."""
+    """Bytes of projection weight a decode session holds, bf16 beside fp8 and mxfp4: ``gpt2`` from
+    real sessions (with the relative logit error of the quantised sessions' last step against the
+    unquantised model, random init), the Llama-2-7B shape from its projection shapes alone."""
     from orion_amd.models.llama import build_llama
     torch.manual_seed(0)
     model = build_gpt2("gpt2").to("cuda").to(torch.bfloat16).eval()
     prompt = torch.randint(0, 50257, (8, 64), device="cuda")
     s16, s8 = model.decode_session(8, 128), model.decode_session(8, 128, weights="fp8")
-    a, b = s16.prefill(prompt).float(), s8.prefill(prompt).float()
+    s4 = model.decode_session(8, 128, weights="mxfp4")
+    a, b, c = s16.prefill(prompt).float(), s8.prefill(prompt).float(), s4.prefill(prompt).float()
     for tok in torch.randint(0, 50257, (16, 8, 1), device="cuda"):
-        a, b = s16.step(tok).float(), s8.step(tok).float()
+        a, b, c = s16.step(tok).float(), s8.step(tok).float(), s4.step(tok).float()
     res = dict(bench="decode_weight_bytes", gpt2_bf16_mbytes=round(s16.weight_bytes / 1e6, 1),
                gpt2_fp8_mbytes=round(s8.weight_bytes / 1e6, 1),
-               gpt2_fp8_rel_logit_err_vs_bf16_random_init=round(((a - b).norm() / a.norm()).item(), 4))
+               gpt2_fp8_rel_logit_err_vs_bf16_random_init=round(((a - b).norm() / a.norm()).item(), 4),
+               gpt2_mxfp4_mbytes=round(s4.weight_bytes / 1e6, 1),
+               gpt2_mxfp4_rel_logit_err_vs_bf16_random_init=round(((a - c).norm() / a.norm()).item(), 4))
     with torch.device("meta"):
         shapes = [tuple(w.shape) for _, w in build_llama("llama2-7b").decode_projections()]
     res["llama2_7b_bf16_mbytes"] = round(sum(2 * n * k for n, k in shapes) / 1e6, 1)
     res["llama2_7b_fp8_mbytes"] = round(sum(n * k + 4 * n for n, k in shapes) / 1e6, 1)
+    res["llama2_7b_mxfp4_mbytes"] = round(sum(n * k // 2 + n * k // 32 for n, k in shapes) / 1e6, 1)
     print(json.dumps(res), flush=True)
 
 
